@@ -2,10 +2,14 @@
 """
 bench.py -- mesh-pairs/s of the matching hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fmap|simnn|zoomout|stress|icp]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload fmap|simnn|zoomout|stress|icp] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch of synthetic mesh pairs that is
-already resident in HBM.  Default workload = BASELINE.json configs[1]:
+already resident in HBM.  A plain run sets up, warms up, times exactly K steps, writes the
+last step's outputs (--dump-outputs DIR: DIR/<name>.npy, float32 / float64, at most 64 MB;
+the seeded inputs are the same from run to run) and prints the line.  Everything else below
+(roofline, per-kernel tables, parity, the other configs, cpu_baseline) needs --full.
+Default workload = BASELINE.json configs[1]:
     batch = 64 pairs per GPU, N = 2048 vertices (64x32 torus), D = 768 fp16 descriptors,
     k = 128 eigenfunctions:  project -> pinned column -> functional-map solve -> four vertex maps.
 Pairs are independent: with N GPUs every rank processes its own 64 pairs (weak scaling, no
@@ -15,7 +19,7 @@ data-path collective); the process group (RCCL) is used only for the timing barr
 (python -m torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1).  Under an
 external torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE as usual.
 
-Prints ONE JSON line (rank 0) with the driver's contract keys plus
+Prints ONE JSON line (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step, steps, config ...; --full adds
     roofline      the kernel that takes the largest share of the step (per-kernel HIP-event table of an untimed pass of the
                   same step; its launch time inside the timed region), priced on SURVEY 8(d)'s ALGORITHMIC flops against the
                   spec peak of the arithmetic it runs in, with
@@ -61,15 +65,21 @@ WORKLOADS = {
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 20; surface_map: 3 calls)")
+    ap.add_argument("--warmup", type=int, default=None, help="untimed steps before them (default 3; surface_map: 1 call)")
     ap.add_argument("--workload", default="fmap", choices=list(WORKLOADS))
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0) as DIR/<name>.npy: float64 for float64 results and integer maps, "
+                         "float32 otherwise; a seeded sample of the pairs where the whole exceeds 64 MB")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline and per-kernel tables, timing blocks, parity, PCIe-inclusive "
+                         "rate, the other configs, the CPU baseline")
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU (default: the config's)")
     ap.add_argument("--basis", default="f64", choices=["f64", "f32"],
                     help="dtype of the eigenvectors and masses handed to the path: f64 = what the reference holds and consumes "
                          "(TriMesh / FM_to_p2p run on float64; the *_f64 entry points), f32 = pre-rounded inputs (round-1/2 benches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[2] similarity-kernel block of the default workload")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the other configs' blocks of the default workload")
     ap.add_argument("--p2p-split", type=int, default=None,
                     help="code path of the four maps (dm_set_option p2p_split): 0 float64 kernel, 1 two fp16 passes, 2 one pass in both "
                          "directions (3: its 4-wave shape); default: the library's")
@@ -79,7 +89,15 @@ def parse_args():
                          "the N > 1 branch of the timing code on a 1-GPU box (tests/test_gpu_shard.py)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal of the N > 1 path on a 1-GPU box: every rank uses cuda:0, gloo carries the barrier")
-    return ap.parse_args()
+    args = ap.parse_args()
+    one_pair = args.workload == "surface_map"
+    if args.steps is None:
+        args.steps = 3 if one_pair else 20
+    if args.warmup is None:
+        args.warmup = 1 if one_pair else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -96,14 +114,18 @@ def self_launch(args):
 
 
 def make_batch(w, rank, basis="f64"):
+    from threadpoolctl import threadpool_limits
     from densematcher_amd import synth
     n = w["nu"] * w["nv"]
     rdt = np.float64 if basis == "f64" else np.float32
     if w["k"]:
         # N = 8192: a mass-orthonormalised seeded Gaussian stands in for the eigenbasis (throughput-only
-        # runs; an ARPACK solve per mesh would dominate the set-up and the arithmetic does not depend on it)
-        batch = synth.make_pair_batch(w["B"], w["nu"], w["nv"], max(w["D"], 8), w["k"], sigma=0.1, n_distinct_meshes=2,
-                                      seed0=100 * rank, basis="eig" if n <= 4096 else "random", real_dtype=rdt)
+        # runs; an ARPACK solve per mesh would dominate the set-up and the arithmetic does not depend on it).
+        # One BLAS thread: the unperturbed torus has repeated eigenvalues, and which basis of such an eigenspace the solver
+        # returns depends on how its products are split over threads; the inputs must not change with the thread count.
+        with threadpool_limits(limits=1, user_api="blas"):
+            batch = synth.make_pair_batch(w["B"], w["nu"], w["nv"], max(w["D"], 8), w["k"], sigma=0.1, n_distinct_meshes=2,
+                                          seed0=100 * rank, basis="eig" if n <= 4096 else "random", real_dtype=rdt)
     else:
         batch = simnn_features(w["B"], n, w["D"], rank)
     return batch
@@ -222,13 +244,7 @@ def timed_kernel(eng, step, kernel, steps, warmup, barrier, n_blocks=N_BLOCKS, m
     in it, their summed ms, [every block's elapsed s]).
     Before the warm-up the same step runs untimed for PREHEAT_S seconds: the part raises its clocks only after some tens of
     milliseconds of sustained load (the first launches of a process run ~20 % slower)."""
-    import torch
-    t0 = time.perf_counter()
-    while time.perf_counter() - t0 < PREHEAT_S:
-        step()
-        torch.cuda.synchronize()
-    for _ in range(warmup):
-        step()
+    warm_up(step, warmup)
     blocks = []
     for _ in range(n_blocks):
         barrier()
@@ -248,6 +264,66 @@ def timed_kernel(eng, step, kernel, steps, warmup, barrier, n_blocks=N_BLOCKS, m
     order = sorted(range(n_blocks), key=lambda i: blocks[i][0])
     med = blocks[order[n_blocks // 2]]
     return med[0], med[1], med[2], [b[0] for b in blocks]
+
+
+def warm_up(step, warmup):
+    """PREHEAT_S seconds of the step (clocks up), then `warmup` steps, all untimed"""
+    import torch
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < PREHEAT_S:
+        step()
+        torch.cuda.synchronize()
+    for _ in range(warmup):
+        step()
+
+
+def timed_steps(step, steps, warmup, barrier, max_over_ranks):
+    """The headline: after warm_up, exactly `steps` steps bracketed by barrier() (barrier + device synchronisation) on both sides,
+    nothing else inside.  Returns (elapsed s, the max over ranks; what the last step returned)."""
+    warm_up(step, warmup)
+    barrier()
+    t0 = time.perf_counter()
+    for _ in range(steps - 1):
+        step()
+    last = step()
+    barrier()
+    return max_over_ranks(time.perf_counter() - t0), last
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(obj, name, out):
+    """every tensor / array in a result into out[name] as a host array: dicts by key, tuples and lists by position"""
+    import torch
+    if isinstance(obj, dict):
+        for key, v in obj.items():
+            output_arrays(v, f"{name}_{key}" if name else str(key), out)
+    elif isinstance(obj, (tuple, list)):
+        for i, v in enumerate(obj):
+            output_arrays(v, f"{name}_{i}", out)
+    elif isinstance(obj, torch.Tensor):
+        t = obj.detach()
+        out[name] = (t if t.dtype == torch.float64 or not t.is_floating_point() else t.float()).cpu().numpy()
+    elif isinstance(obj, np.ndarray) and obj.dtype.kind in "fiub":
+        out[name] = obj
+    return out
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float64 for float64 results and integer maps (exact), float32 for narrower floats.
+    Above DUMP_LIMIT_BYTES in all, every array keeps the same seeded sample of its leading-axis rows (the pairs).  Returns the names."""
+    arrays = {n: (a if a.dtype == np.float64 else a.astype(np.float32 if a.dtype.kind == "f" else np.float64)) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        for n, a in arrays.items():
+            if a.ndim:
+                rows = np.random.default_rng(0).permutation(a.shape[0])[:max(1, int(a.shape[0] * DUMP_LIMIT_BYTES / total))]
+                arrays[n] = a[np.sort(rows)]
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(a))
+    return sorted(arrays)
 
 
 NOTEBOOK_FIT = dict(w_descr=1e4, w_lap=1e3, w_dcomm=0, w_ent=1e-1, w_sumto1=1e1, optinit="zeros", maxiter=5000)   # example.ipynb cell 11
@@ -309,34 +385,42 @@ def surface_map_workload(args):
         dt, res = one_call()
         times.append(dt)
     t = float(np.median(times[args.warmup:]))
-    # per-stage times from a separate instrumented call: every stage bracketed by device synchronisations, the three assignments as one
-    # batched call at the end (the stages add up to more than the clean call: nothing overlaps there)
-    saved = [(o, n, getattr(o, n)) for o, n, _ in patched]
-    for o, n, label in patched:
-        setattr(o, n, timed(label, getattr(o, n)))
-    fmod.EARLY_ASSIGNMENTS = False
-    try:
-        stages.clear()
-        t_instr, _ = one_call()
-        last_stages = dict(stages)
-    finally:
-        fmod.EARLY_ASSIGNMENTS = True
-        for o, n, fn in saved:
-            setattr(o, n, fn)
     model = res[7]
     out = {"metric": "compute_surface_map calls/sec (one pair at a time, notebook parameters)", "value": round(1.0 / t, 4), "unit": "mesh-pairs/s",
            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * t, 2), "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f64", "data": "synthetic",
            "config": {"workload": w["cfg"], "pairs_per_gpu": 1, "N": nu * nv, "D": D, "k": k},
-           "stages_ms": {n: round(1e3 * v, 2) for n, v in last_stages.items()},
-           "stages_note": "from a separate instrumented call (%.1f ms: every stage bracketed by device synchronisations, the three assignments as one "
-                          "batched call at the end); in the timed calls the fitted map's and the precise map's assignments run on side streams "
-                          "beside the later stages" % (1e3 * t_instr),
            "fit": {"iterations": int(model.fit_result.nit[0]), "evaluations": int(model.fit_result.nfev[0]), "status": model.fit_result.message[0]},
            "roofline": {"bound": "latency", "kernel": None, "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None,
                         "note": "a single pair cannot fill the chip: this workload reports the latency of the API; the throughput kernels are in the default workload"}}
-    if not args.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_surface_map(v1, f1, v2, f2, F1, F2, k)
+    if args.dump_outputs:
+        names = ("p2p_21", "p2p_12", "hungarian", "hungarian_precise", "p2p_21_icp", "p2p_12_icp", "hungarian_icp", "model", "mesh1", "mesh2",
+                 "p2p_21_adjoint", "p2p_12_adjoint", "p2p_21_icp_adjoint", "p2p_12_icp_adjoint")
+        arrays = output_arrays(dict(zip(names, res)), "", {})
+        output_arrays(model.FM, "FM", arrays)
+        out["outputs"] = dump_outputs(args.dump_outputs, arrays)
+    del res, model
+    if args.full:
+        # per-stage times from a separate instrumented call: every stage bracketed by device synchronisations, the three assignments as one
+        # batched call at the end (the stages add up to more than the clean call: nothing overlaps there)
+        saved = [(o, n, getattr(o, n)) for o, n, _ in patched]
+        for o, n, label in patched:
+            setattr(o, n, timed(label, getattr(o, n)))
+        fmod.EARLY_ASSIGNMENTS = False
+        try:
+            stages.clear()
+            t_instr, _ = one_call()
+            last_stages = dict(stages)
+        finally:
+            fmod.EARLY_ASSIGNMENTS = True
+            for o, n, fn in saved:
+                setattr(o, n, fn)
+        out["stages_ms"] = {n: round(1e3 * v, 2) for n, v in last_stages.items()}
+        out["stages_note"] = ("from a separate instrumented call (%.1f ms: every stage bracketed by device synchronisations, the three assignments as "
+                              "one batched call at the end); in the timed calls the fitted map's and the precise map's assignments run on side streams "
+                              "beside the later stages" % (1e3 * t_instr))
+        if not args.no_cpu_baseline:
+            out["cpu_baseline"] = cpu_surface_map(v1, f1, v2, f2, F1, F2, k)
     print(json.dumps(out), flush=True)
 
 
@@ -388,8 +472,6 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
     if args.workload == "surface_map":
-        if args.steps == 20:
-            args.steps, args.warmup = 3, 1
         return surface_map_workload(args)
 
     import torch
@@ -438,6 +520,7 @@ def main():
     if args.workload in ("fmap", "stress"):
         def step():
             return sharded("match", dev, k=k)
+        out_name = ""
         split = eng.p2p_split_active(N, N, k)
         maps_kernel = ("simnn4_f16_mfma" if split >= 2 else "simnn2_f16_mfma") if split else "gred_f64"
         dtype = "f16" if split else "f64"
@@ -446,6 +529,7 @@ def main():
 
         def step():
             return sharded("simnn", sim_in)["nn21"]
+        out_name = "nn21"
         dtype = "f16"
     elif args.workload == "icp":
         gen = torch.Generator(device=eng.device).manual_seed(1 + rank)
@@ -455,6 +539,7 @@ def main():
 
         def step():
             return sharded("icp", icp_in, nit=10)["C"]
+        out_name = "C"
         dtype = "f16"
         models.update(refine_models("icp", N, k, B, eng))
     else:
@@ -464,6 +549,7 @@ def main():
 
         def step():
             return sharded("zoomout", zo_in, nit=nit, step=1)["C"]
+        out_name = "C"
         dtype = "f16"
         models.update(refine_models("zoomout", N, k, B, eng))
 
@@ -479,28 +565,52 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    # which kernel dominates the step: one untimed pass with every launch bracketed by HIP events
+    # which kernel dominates the step (its arithmetic is the line's dtype): untimed steps with every launch bracketed by HIP events
     wl_tag = args.workload if not args.batch else None
     dominant = dominant_kernel(eng, step)
-    blocks_local = []
-    elapsed, launches, kernel_ms, blocks = timed_kernel(eng, step, dominant, args.steps, args.warmup, barrier, max_over_ranks=max_over_ranks,
-                                                        local_out=blocks_local)
-    # the per-kernel table, every kernel timed on its own, after the timed region
-    table_steps = 2 if args.workload == "zoomout" else 10
-    table, kernel_ms_per_step, launches_per_step = kernel_table(eng, step, table_steps, models, wl_tag, step_ms=1e3 * elapsed / args.steps)
     if models.get(dominant):
         dtype = models[dominant]["dtype"]          # the arithmetic type of the kernel that dominates the step
-
+    # the headline: exactly `steps` steps, nothing bracketed inside
+    elapsed, last = timed_steps(step, args.steps, args.warmup, barrier, max_over_ranks)
     value = B * world * args.steps / elapsed
+    group_size = dist.get_world_size() if dist is not None else 1
+    out = {
+        "metric": "mesh-pairs/sec at N=2048 D=768 k=128" if args.workload == "fmap" else f"mesh-pairs/sec ({args.workload})",
+        "value": round(value, 2), "unit": "mesh-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "ms_per_pair": round(1e3 * elapsed / (B * args.steps), 5),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
+        "inputs": "device-resident (uploaded before the timed region; outputs stay on the device)",
+        "config": {"workload": w["cfg"], "pairs_per_gpu": B, "N": N, "D": D, "k": k,
+                   "basis_dtype": str(host["Phi1"].dtype) if "Phi1" in host else None,
+                   "parallelism": f"pairs sharded over {world} GPU(s), one process per GPU, no data-path collective",
+                   "process_group": (backend if dist is not None else None), "process_group_size": group_size},
+        "timing": {"reported": "one block of exactly `steps` steps after `warmup` untimed ones, bracketed by barrier + synchronize (max over ranks)"},
+    }
+    if args.dump_outputs and rank == 0:
+        out["outputs"] = dump_outputs(args.dump_outputs, output_arrays(last, out_name, {}))
+    del last
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # --full: five more blocks of `steps` steps with the dominant kernel's launches bracketed by HIP events (the roofline's kernel time;
+    # the median block prices the tables' share of the step)
+    blocks_local = []
+    median_s, launches, kernel_ms, blocks = timed_kernel(eng, step, dominant, args.steps, args.warmup, barrier, max_over_ranks=max_over_ranks,
+                                                         local_out=blocks_local)
+    # the per-kernel table, every kernel timed on its own, after the timed region
+    table_steps = 2 if args.workload == "zoomout" else 10
+    table, kernel_ms_per_step, launches_per_step = kernel_table(eng, step, table_steps, models, wl_tag, step_ms=1e3 * median_s / args.steps)
     avg_ms = kernel_ms / max(launches, 1)
     roof = roofline_block(dominant, models.get(dominant), launches, avg_ms, wl_tag, table, kernel_ms_per_step, launches_per_step, eng)
     kernels_table = roof.pop("kernels")
     # per-rank figures: every rank's five timed blocks, gathered over the process group when there is one
     my_blocks = [round(1e3 * b_ / args.steps, 4) for b_ in blocks_local]
     per_rank = {str(rank): my_blocks}
-    group_size = 1
     if dist is not None:
-        group_size = dist.get_world_size()
         gathered = [None] * group_size
         dist.all_gather_object(gathered, my_blocks)
         per_rank = {str(r): g for r, g in enumerate(gathered)}
@@ -540,24 +650,14 @@ def main():
                                           "batched_streams": (sm.get("batched") or {}).get("streams"),
                                           "robust_laplacian": "restated (opt-in: the robust_laplacian wheel is not installed on the box)",
                                           "error": sm.get("error") or (sm.get("batched") or {}).get("error")}
-    # ---- the line.  The driver keeps the LAST 2 000 characters of it: the contract's keys come first, the long tables (`details`) in the
-    # middle, and `roofline`, `cpu_baseline` and a compact `summary` (every secondary figure, <= 1 500 characters) at the very end
-    out = {
-        "metric": "mesh-pairs/sec at N=2048 D=768 k=128" if args.workload == "fmap" else f"mesh-pairs/sec ({args.workload})",
-        "value": round(value, 2), "unit": "mesh-pairs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4), "ms_per_pair": round(1e3 * elapsed / (B * args.steps), 5),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dtype, "data": "synthetic",
-        "inputs": "device-resident (uploaded before the timed region; outputs stay on the device)",
-        "pcie_inclusive_value": pcie["value"] if pcie else None,
-        "config": {"workload": w["cfg"], "pairs_per_gpu": B, "N": N, "D": D, "k": k,
-                   "basis_dtype": str(host["Phi1"].dtype) if "Phi1" in host else None,
-                   "parallelism": f"pairs sharded over {world} GPU(s), one process per GPU, no data-path collective",
-                   "process_group": (backend if dist is not None else None), "process_group_size": group_size},
-    }
-    out["timing"] = {"blocks": N_BLOCKS, "reported": "median block of exactly `steps` steps, each block bracketed by barrier + synchronize (max over ranks per block)",
-                     "blocks_ms_per_step": [round(1e3 * b_ / args.steps, 4) for b_ in blocks], "blocks_ms_per_step_by_rank": per_rank,
-                     "kernel_ms_per_step_note": "kernel_ms_per_step in `roofline` is a sum of single-kernel HIP-event brackets taken after the timed "
-                                                "region: the brackets add about 2 %, so it can exceed ms_per_step"}
+    # ---- the rest of the line.  Only its LAST 2 000 characters may be kept: the contract's keys come first, the long tables (`details`) in
+    # the middle, and `roofline`, `cpu_baseline` and a compact `summary` (every secondary figure, <= 1 500 characters) at the very end
+    out["pcie_inclusive_value"] = pcie["value"] if pcie else None
+    out["timing"].update({"blocks": N_BLOCKS, "blocks_reported": "after the headline: blocks of exactly `steps` steps with the dominant kernel's "
+                                                                  "launches bracketed by HIP events, each bracketed by barrier + synchronize (max over ranks per block)",
+                          "blocks_ms_per_step": [round(1e3 * b_ / args.steps, 4) for b_ in blocks], "blocks_ms_per_step_by_rank": per_rank,
+                          "kernel_ms_per_step_note": "kernel_ms_per_step in `roofline` is a sum of single-kernel HIP-event brackets taken after the timed "
+                                                     "region: the brackets add about 2 %, so it can exceed ms_per_step"})
     if pcie:
         out["pcie_inclusive"] = pcie
     if args.workload == "fmap" and not args.batch and rank == 0:
@@ -819,7 +919,7 @@ def secondary_surface_map():
     import io
     import contextlib
     buf = io.StringIO()
-    a = argparse.Namespace(steps=3, warmup=1, no_cpu_baseline=True)
+    a = argparse.Namespace(steps=3, warmup=1, no_cpu_baseline=True, full=True, dump_outputs=None)
     try:
         with contextlib.redirect_stdout(buf):
             surface_map_workload(a)
