@@ -167,7 +167,7 @@ extern "C" int dm_profile_kernel(dm_ctx* ctx, const char* name) {
     return DM_OK;
 }
 
-int dm_prof_begin(dm_ctx* ctx, const char* name) {
+int dm_prof_begin(dm_ctx* ctx, const char* name, const char* sym) {
     if (ctx->prof_name.empty() || (ctx->prof_name != "*" && ctx->prof_name != name)) return -1;
     if (ctx->prof_used + 2 > ctx->prof_events.size()) {
         for (int i = 0; i < 2; ++i) {
@@ -178,7 +178,9 @@ int dm_prof_begin(dm_ctx* ctx, const char* name) {
     }
     int tok = (int)ctx->prof_used;
     if (ctx->prof_names.size() < ctx->prof_events.size() / 2) ctx->prof_names.resize(ctx->prof_events.size() / 2);
+    if (ctx->prof_syms.size() < ctx->prof_events.size() / 2) ctx->prof_syms.resize(ctx->prof_events.size() / 2);
     ctx->prof_names[tok / 2] = name;
+    ctx->prof_syms[tok / 2] = sym;
     (void)hipEventRecord(ctx->prof_events[tok], ctx->stream);
     ctx->prof_used += 2;
     return tok;
@@ -207,28 +209,33 @@ extern "C" int dm_profile_read(dm_ctx* ctx, int* launches, double* total_ms) {
     return DM_OK;
 }
 
-// every launch since dm_profile_kernel(ctx, "*") (or the one named kernel), aggregated by name in order of first launch
+// every launch since dm_profile_kernel(ctx, "*") (or the one named kernel), aggregated by name in order of first launch; the last
+// column lists the distinct kernel expressions launched under that name (';'-separated, in order of first launch)
 extern "C" int dm_profile_report(dm_ctx* ctx, char* buf, size_t cap) {
     if (!ctx || !buf || cap == 0) return DM_EINVAL;
     DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     std::vector<std::string> names;
     std::vector<int> count;
     std::vector<double> total;
+    std::vector<std::string> syms;
     for (size_t i = 0; i + 1 < ctx->prof_used; i += 2) {
         float ms = 0.f;
         DM_CHECK_HIP(ctx, hipEventElapsedTime(&ms, ctx->prof_events[i], ctx->prof_events[i + 1]));
         const std::string n = ctx->prof_names[i / 2] ? ctx->prof_names[i / 2] : "?";
         size_t q = 0;
         while (q < names.size() && names[q] != n) ++q;
-        if (q == names.size()) { names.push_back(n); count.push_back(0); total.push_back(0.0); }
+        if (q == names.size()) { names.push_back(n); count.push_back(0); total.push_back(0.0); syms.emplace_back(); }
         count[q] += 1;
         total[q] += ms;
+        const std::string k = ctx->prof_syms[i / 2] ? ctx->prof_syms[i / 2] : "?";
+        if ((";" + syms[q] + ";").find(";" + k + ";") == std::string::npos) syms[q] += (syms[q].empty() ? "" : ";") + k;
     }
     std::string out;
     for (size_t q = 0; q < names.size(); ++q) {
         char line[256];
-        snprintf(line, sizeof(line), "%s\t%d\t%.6f\n", names[q].c_str(), count[q], total[q]);
+        snprintf(line, sizeof(line), "%s\t%d\t%.6f\t", names[q].c_str(), count[q], total[q]);
         out += line;
+        out += syms[q] + "\n";
     }
     if (out.size() + 1 > cap) return dm_fail(ctx, DM_EINVAL, "dm_profile_report: buffer of %zu bytes too small (%zu needed)", cap, out.size() + 1);
     memcpy(buf, out.c_str(), out.size() + 1);

@@ -31,6 +31,7 @@ struct dm_ctx {
     std::string prof_name;
     std::vector<hipEvent_t> prof_events;   // pairs (start, stop)
     std::vector<const char*> prof_names;   // name of the launch each pair brackets (string literals of DM_LAUNCH)
+    std::vector<const char*> prof_syms;    // the kernel expression of that launch (DM_LAUNCH's `kernel` argument as written)
     size_t prof_used = 0;                  // events used so far
 
     // largest dynamic-LDS size already granted to each kernel on this device (hipFuncSetAttribute is per device)
@@ -120,13 +121,14 @@ static inline size_t dm_align_up(size_t x, size_t a = 256) { return (x + a - 1) 
 // ---- launch bookkeeping -----------------------------------------------------
 // DM_LAUNCH(ctx, "name", kernel, grid, block, shmem, args...) launches on the
 // ctx stream, brackets with events when `name` is being profiled, and returns
-// DM_EHIP from the enclosing function on a launch error.
-int dm_prof_begin(dm_ctx* ctx, const char* name);
+// DM_EHIP from the enclosing function on a launch error.  The profiler also keeps
+// the kernel expression itself (#kernel): several kernels share one name.
+int dm_prof_begin(dm_ctx* ctx, const char* name, const char* sym);
 int dm_prof_end(dm_ctx* ctx, int token);
 
 #define DM_LAUNCH(ctx, name, kernel, grid, block, shmem, ...)                          \
     do {                                                                               \
-        int _tok = dm_prof_begin(ctx, name);                                           \
+        int _tok = dm_prof_begin(ctx, name, #kernel);                                   \
         hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->stream, __VA_ARGS__);    \
         hipError_t _le = hipGetLastError();                                            \
         if (_le != hipSuccess)                                                         \

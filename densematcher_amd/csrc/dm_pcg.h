@@ -19,6 +19,12 @@
 // n = 127, all of them matrix instructions.
 // A workgroup that does not reach the tolerance in `maxit` steps, or meets a non-positive curvature (the matrix is not positive
 // definite), raises the pair's flag: the caller then runs the direct solver on the flagged pairs (it also reports singular systems).
+// Accuracy: the stopping test reads the RECURRENCE residual, never b - M x, so the iteration promises no fixed distance to the direct
+// solution; what it delivers depends on the condition number kappa of the system.  tests/test_gpu_solver_conditioning.py holds every
+// system it accepts to |x - x_exact|_inf <= max(1e-9, 4 (n + D) u kappa) |x_exact|_inf (u = 2^-53, D descriptor channels); measured:
+// 1.7e-11 at kappa ~ 4, <= 0.29 (n + D) u kappa up to kappa ~ 1e15, e.g. 5e-5 at kappa 5e10 for two near-dependent rows of A under a
+// repeated eigenvalue (the direct solvers: 6e-5 there, <= 0.04 (n + D) u kappa everywhere).  Rank-deficient descriptors, and
+// near-dependent rows where the rest of the spectrum is spread, leave it at the six-step gate.
 #pragma once
 #include "dm_device.h"
 

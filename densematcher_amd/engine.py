@@ -90,8 +90,11 @@ class MatchEngine:
                        "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1}
 
     def set_option(self, name, value):
-        """Choose between equivalent code paths of the library (include/densematch.h: dm_set_option); every setting
-        returns the same, exact results."""
+        """Choose between code paths of the library (include/densematch.h: dm_set_option).  Most settings return the same
+        results bit for bit; "solve_pcg" (the batched iteration in front of the direct solvers) changes bits: its C agrees with
+        solve_pcg = 0 to max(1e-9, 4 (n + D) u kappa) relative per system of condition number kappa (u = 2^-53,
+        tests/test_gpu_solver_conditioning.py); "fit_f32" runs the fused fit's element loop in fp32 (the reference's precision) and
+        "fit_mfma" chooses the summation order of its products, so both change the fused fit's bits."""
         self._chk(self.lib.dm_set_option(self.ctx, name.encode(), int(value)))
 
     def reset_options(self):
@@ -135,14 +138,16 @@ class MatchEngine:
         self._chk(self.lib.dm_measure_peak(self.ctx, self.PEAK_PROBES[which], C.byref(v)))
         return v.value
 
-    def profile_report(self):
-        """after profile_kernel("*"): {kernel name: (launches, total ms)} of every launch since, in order of first launch"""
+    def profile_report(self, kernels=False):
+        """after profile_kernel("*"): {kernel name: (launches, total ms)} of every launch since, in order of first launch;
+        kernels=True adds a third entry, the tuple of distinct kernel expressions launched under that name (e.g.
+        "fmap_solve_reg_kernel<8>" under "fmap_solve_chol")"""
         buf = C.create_string_buffer(1 << 16)
         self._chk(self.lib.dm_profile_report(self.ctx, buf, len(buf)))
         out = {}
         for line in buf.value.decode().splitlines():
-            name, n, ms = line.split("\t")
-            out[name] = (int(n), float(ms))
+            name, n, ms, syms = line.split("\t")
+            out[name] = (int(n), float(ms), tuple(syms.split(";"))) if kernels else (int(n), float(ms))
         return out
 
     # ------------------------------------------------------------------ ops
@@ -217,8 +222,9 @@ class MatchEngine:
                     f"(row {int(info[bad[0]]) - 1}): descriptors are rank deficient in the basis and w_lap cannot fix it")
         return Cm
 
-    def fmap_solve(self, A, Bm, lam1, lam2, c00, w_descr, w_lap, check=True):
-        """Closed-form minimiser of the w_descr / w_lap energy -> C (B,k2,k1) f64."""
+    def fmap_solve(self, A, Bm, lam1, lam2, c00, w_descr, w_lap, check=True, return_info=False):
+        """Closed-form minimiser of the w_descr / w_lap energy -> C (B,k2,k1) f64; return_info=True: (C, info (B,) int32), info[b] =
+        1 + the index of a row of C whose system is not positive definite (0: every system of pair b was solved)."""
         A = self._dev(A, torch.float32, "A")
         Bm = self._dev(Bm, torch.float32, "Bm")
         lam1 = self._dev(lam1, torch.float64, "lam1")
@@ -238,7 +244,7 @@ class MatchEngine:
                 raise _lib.DenseMatchError(
                     f"functional-map system not positive definite for pairs {bad.tolist()[:8]} "
                     f"(row {int(info[bad[0]]) - 1}): descriptors are rank deficient in the basis and w_lap cannot fix it")
-        return Cm
+        return (Cm, info) if return_info else Cm
 
     WEIGHT_ORDER = ("w_descr", "w_lap", "w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal")
 

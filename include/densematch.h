@@ -118,8 +118,9 @@ int dm_last_requeued_rows(dm_ctx* ctx, int out[4]);
 int dm_profile_kernel(dm_ctx* ctx, const char* name);
 int dm_profile_read(dm_ctx* ctx, int* launches, double* total_ms);
 /* dm_profile_kernel(ctx, "*") brackets EVERY launch; dm_profile_report then writes one line per kernel name,
- * "name\tlaunches\ttotal_ms\n" in order of first launch, into buf (NUL-terminated; DM_EINVAL if cap is too small) and
- * resets the record.  (The event pairs add a few microseconds between launches: bench.py times its K steps with one kernel
+ * "name\tlaunches\ttotal_ms\tkernels\n" in order of first launch, into buf (NUL-terminated; DM_EINVAL if cap is too small) and
+ * resets the record.  `kernels` lists the distinct kernel expressions launched under that name, ';'-separated (several kernels
+ * share a name: every direct solver is "fmap_solve_chol").  (The event pairs add a few microseconds between launches: bench.py times its K steps with one kernel
  * bracketed and collects the per-kernel table in a separate, untimed pass.) */
 int dm_profile_report(dm_ctx* ctx, char* buf, size_t cap);
 

@@ -132,6 +132,50 @@ def fmap_solve(A, B, lam1, lam2, x0, w_descr, w_lap):
     return C
 
 
+def fmap_solve_refined(A, B, lam1, lam2, c00, w_descr, w_lap, steps=3):
+    """`fmap_solve` to (nearly) the last bit of the EXACT solution of the systems
+    the library receives: A, B as given (fp32 arrays are taken exactly), P, Q,
+    the matrices and every residual formed in np.longdouble, a float64 Cholesky
+    factor, `steps` rounds of iterative refinement.  x0 = (c00, 0, ..., 0)^T.
+    Returns (C (k2,k1) float64, kappa (k2,)): kappa[i] = 2-norm condition number
+    of system i (eigvalsh; inf when it is not numerically positive definite; such
+    rows of C are NaN).  Accuracy (pinned against mpmath in
+    tests/test_oracle_golden.py): |x - x_exact|_inf <= (2 u + 8 (n + D) u_ld kappa) |x_exact|_inf,
+    u = 2^-53, u_ld = the longdouble epsilon (2^-64 on x86: 80-bit extended)."""
+    ld = np.longdouble
+    A = np.asarray(A)
+    B = np.asarray(B)
+    k1, k2 = A.shape[0], B.shape[0]
+    n = k1 - 1
+    Al, Bl = A.astype(ld), B.astype(ld)
+    P = ld(w_descr) * (Al @ Al.T)
+    Q = ld(w_descr) * (Bl @ Al.T)
+    dd = ld(w_lap) * ev_sqdiff(lam1, lam2).astype(ld)[:, 1:]          # (k2, n)
+    Pff = P[1:, 1:]
+    rhs = Q[:, 1:].copy()
+    rhs[0] -= P[1:, 0] * ld(c00)
+    M64 = Pff.astype(np.float64)[None] + np.einsum("ij,jk->ijk", dd.astype(np.float64), np.eye(n))
+    ev = np.linalg.eigvalsh(M64)
+    kappa = np.where(ev[:, 0] > 0, ev[:, -1] / np.where(ev[:, 0] > 0, ev[:, 0], 1.0), np.inf)
+    C = np.zeros((k2, k1))
+    C[0, 0] = c00
+    for i in range(k2):
+        if not np.isfinite(kappa[i]):
+            C[i, 1:] = np.nan
+            continue
+        try:
+            fac = scipy.linalg.cho_factor(M64[i], lower=True)
+        except np.linalg.LinAlgError:
+            C[i, 1:] = np.nan
+            continue
+        x = scipy.linalg.cho_solve(fac, rhs[i].astype(np.float64)).astype(ld)
+        for _ in range(steps):
+            r = rhs[i] - (Pff @ x + dd[i] * x)
+            x = x + scipy.linalg.cho_solve(fac, r.astype(np.float64)).astype(ld)
+        C[i, 1:] = x.astype(np.float64)
+    return C, kappa
+
+
 def fit(phi1, phi2, lam1, lam2, a1, a2, F1, F2, w_descr, w_lap, optinit="zeros"):
     """FunctionalMapping.fit restated (w_descr / w_lap terms only)
     -- pyFM/functional.py:352-487.  Returns C (k2,k1) float64."""

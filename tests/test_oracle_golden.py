@@ -248,3 +248,43 @@ def test_zoomout_config4_full_length_against_reference(fx_cfg4):
     C, p21 = orc.zoomout_refine(fx["C0"], phi1, phi2, nit=int(fx["nit"]), step=1, a2=a2, return_p2p=True)
     assert np.array_equal(p21, fx["p21_zo"])
     assert np.abs(C - fx["C_zo"]).max() < 1e-9
+
+
+@pytest.mark.parametrize("eps", [1e-1, 1e-3, 1e-5])
+def test_fmap_solve_refined_against_mpmath(eps):
+    """the conditioning tests' reference (fmap_solve_refined: longdouble P, Q and residuals, float64 Cholesky, iterative refinement)
+    against a 50-digit solve of the same systems: two near-collinear rows of A under a coinciding eigenvalue make kappa ~ 1 / eps^2
+    for the systems whose eigenvalue they share"""
+    import mpmath
+    mpmath.mp.dps = 50
+    rng = np.random.default_rng(int(-np.log10(eps)))
+    k1, k2, D, wd, wl = 10, 5, 7, 1e4, 1e3
+    A = (rng.standard_normal((k1, D)) * 0.1).astype(np.float32)
+    A[4] = A[3] + np.float32(eps) * (rng.standard_normal(D) * 0.1).astype(np.float32)
+    Bm = (rng.standard_normal((k2, D)) * 0.1).astype(np.float32)
+    lam1 = np.sort(rng.uniform(0, 40, k1)); lam1[0] = 0.0; lam1[4] = lam1[3]
+    lam2 = np.sort(rng.uniform(0, 40, k2)); lam2[0] = 0.0; lam2[2] = lam1[3]
+    c00 = -0.75
+    C, kappa = orc.fmap_solve_refined(A, Bm, lam1, lam2, c00, wd, wl)
+    assert C[0, 0] == c00 and np.all(C[1:, 0] == 0)
+    assert kappa.max() >= 0.1 / eps ** 2
+
+    mf = lambda v: mpmath.mpf(float(v))
+    Am = mpmath.matrix([[mf(v) for v in row] for row in A])
+    Bmm = mpmath.matrix([[mf(v) for v in row] for row in Bm])
+    P = mf(wd) * (Am * Am.T)
+    Q = mf(wd) * (Bmm * Am.T)
+    ev = orc.ev_sqdiff(lam1, lam2)
+    n = k1 - 1
+    u, uld = 2.0 ** -53, float(np.finfo(np.longdouble).eps)
+    for i in range(k2):
+        M = mpmath.matrix(n, n)
+        for r in range(n):
+            for c in range(n):
+                M[r, c] = P[r + 1, c + 1] + (mf(wl) * mf(ev[i, r + 1]) if r == c else 0)
+        rhs = mpmath.matrix([Q[i, c + 1] - (P[c + 1, 0] * mf(c00) if i == 0 else 0) for c in range(n)])
+        x = mpmath.lu_solve(M, rhs)
+        xe = np.array([float(v) for v in x])
+        err = np.abs(C[i, 1:] - xe).max() / np.abs(xe).max()
+        print(f"eps {eps:.0e} system {i}: kappa {kappa[i]:.1e} relative error {err:.1e}")
+        assert err <= 2 * u + 8 * (n + D) * uld * kappa[i], (i, kappa[i], err)
