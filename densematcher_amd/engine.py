@@ -30,6 +30,44 @@ class _KeepAlive(tuple):
     """an argument tuple that also holds the tensors its raw pointers refer to"""
 
 
+def heat_geodesic_check(V, F, mass, b=0):
+    """Host checks of one mesh of MatchEngine.heat_geodesic_factor; ValueError where the reference's SuperLU fails or returns
+    numbers that depend on its pivoting:
+    * more than one connected component (vertices that no face references included): W is singular beyond its constant;
+    * lumped masses that are not one third of the adjacent face areas (e.g. those of process(robust=True), the intrinsic
+      Laplacian's): W phi = A div h is then inconsistent -- sum_i A_i div_i = 0 holds only for A_i = va_i, since
+      sum_i va_i div_i = sum_f area_f (sum_c grad phi_c) . h_f = 0 -- and its solution depends on where W is grounded."""
+    import numpy as np
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    V, F = np.asarray(V, np.float64), np.asarray(F, np.int64)
+    n = V.shape[0]
+    if V.ndim != 2 or V.shape[1] != 3:
+        raise ValueError(f"heat_geodesic_factor: mesh {b}: vertices must be (n, 3)")
+    if F.ndim != 2 or F.shape[1] != 3 or F.size == 0 or F.min() < 0 or F.max() >= n:
+        raise ValueError(f"heat_geodesic_factor: mesh {b}: faces must be (m, 3) indices into the {n} vertices")
+    e = np.concatenate([F[:, [0, 1]], F[:, [1, 2]]])
+    G = sp.coo_matrix((np.ones(len(e)), (e[:, 0], e[:, 1])), shape=(n, n))
+    ncomp = connected_components(G, directed=False)[0]
+    if ncomp != 1:
+        raise ValueError(f"heat_geodesic_factor: mesh {b} has {ncomp} connected components (vertices that no face references "
+                         "count as components of their own): the heat method's W is singular beyond its constant there "
+                         "(the reference's SuperLU fails or returns pivot-dependent numbers)")
+    mass = np.asarray(mass, np.float64).ravel()
+    if len(mass) != n:
+        raise ValueError(f"heat_geodesic_factor: mesh {b}: {len(mass)} masses for {n} vertices")
+    area = 0.5 * np.linalg.norm(np.cross(V[F[:, 1]] - V[F[:, 0]], V[F[:, 2]] - V[F[:, 0]]), axis=1)
+    va = np.zeros(n)
+    np.add.at(va, F.ravel(), np.repeat(area / 3.0, 3))
+    dev = np.abs(mass - va)
+    if not np.all(dev <= 1e-8 * va):
+        i = int(np.argmax(np.where(va > 0, dev / np.maximum(va, 1e-300), np.inf)))
+        raise ValueError(f"heat_geodesic_factor: mesh {b}: the lumped mass A is not one third of the adjacent face areas (vertex {i}: "
+                         f"{mass[i]:.6g} against {va[i]:.6g}), as after process(robust=True): W phi = A div h is then inconsistent, "
+                         "and its solution depends on the solver's pivoting (the reference's SuperLU) or on the ground vertex.  Use "
+                         "the cotangent Laplacian's W and A (process(robust=False) on a fresh mesh)")
+
+
 class MatchEngine:
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
@@ -599,6 +637,120 @@ class MatchEngine:
         mass64 = torch.empty((Bn, N), dtype=torch.float64, device=self.device)
         self._chk(self.lib.dm_laplacian_ell(self.ctx, Bn, N, nt, _ptr(rows), nnz, _ptr(nv_d), _ptr(cols), _ptr(vals), _ptr(mass32), _ptr(w), _ptr(mass64)))
         return {"cols": cols, "vals": vals, "mass32": mass32, "w": w, "mass64": mass64, "nnz": nnz, "n_verts": n_verts}
+
+    # ------------------------------------------------------------- heat-method geodesics (dm_heat_geodesic_*)
+    _GEOD_INFO = ((1, "A + tW is not positive definite"),
+                  (2, "the grounded stiffness matrix W is not positive definite (more than one connected component?)"),
+                  (4, "the mesh has a face of zero area"),
+                  (8, "a face index or a column of W lies outside the mesh's vertices"),
+                  (16, "a vertex that no face references"))
+
+    def heat_geodesic_factor(self, meshes, t):
+        """Factor the two systems of the heat method (pyFM geometry.heat_geodmat: A + tW and W, geometry.py:716-718) for a batch
+        of meshes, on the device (dm_heat_geodesic_factor: dense float64 Cholesky, W grounded at vertex 0).
+        meshes: list of (verts (n,3), faces (m,3), W, mass (n,)) with W the stiffness matrix as a SciPy sparse matrix or as the
+        (cols, w) device rows (n, nnz) of laplacian_ell; t: the heat time, one float or one per mesh.  Fails closed (ValueError)
+        on a mesh of more than one connected component (vertices that no face references included), masses that are not one
+        third of the adjacent face areas (heat_geodesic_check), a face of zero area or a system that is not positive definite.  Returns the factors (a dict holding the device buffer) for heat_geodesic."""
+        import numpy as np
+        import scipy.sparse as sp
+        Bn = len(meshes)
+        if Bn == 0:
+            raise ValueError("heat_geodesic_factor: no meshes")
+        ts = np.broadcast_to(np.asarray(t, np.float64), (Bn,)).copy()
+        n_verts, rows = [], []
+        for b, (V, F, W, mass) in enumerate(meshes):
+            heat_geodesic_check(V, F, mass, b)
+            n = len(V)
+            if sp.issparse(W):
+                Wc = sp.csr_matrix(W)
+                if Wc.shape != (n, n):
+                    raise ValueError(f"heat_geodesic_factor: mesh {b}: W is {Wc.shape}, expected {(n, n)}")
+                rl = np.diff(Wc.indptr)
+                w = max(1, int(rl.max()))
+                cols_h = np.full((n, w), -1, np.int32)
+                vals_h = np.zeros((n, w), np.float64)
+                pos = np.arange(Wc.nnz) - np.repeat(Wc.indptr[:-1], rl)
+                r = np.repeat(np.arange(n), rl)
+                cols_h[r, pos] = Wc.indices
+                vals_h[r, pos] = Wc.data
+                rows.append((torch.as_tensor(cols_h).to(self.device), torch.as_tensor(vals_h).to(self.device)))
+            else:
+                cols_d, w_d = W
+                if cols_d.shape[0] != n or w_d.shape != cols_d.shape:
+                    raise ValueError(f"heat_geodesic_factor: mesh {b}: device rows of shape {tuple(cols_d.shape)} for {n} vertices")
+                rows.append((cols_d, w_d))
+            n_verts.append(n)
+        N = max(n_verts)
+        nt = max(len(m[1]) for m in meshes)
+        nnz = max(int(c.shape[1]) for c, _ in rows)
+        tri_h = np.full((Bn, nt, 3), -1, np.int32)
+        vert_h = np.zeros((Bn, N, 3), np.float64)
+        mass_h = np.zeros((Bn, N), np.float64)
+        for b, (V, F, _, mass) in enumerate(meshes):
+            tri_h[b, :len(F)] = F
+            vert_h[b, :len(V)] = V
+            mass_h[b, :len(V)] = np.asarray(mass, np.float64).ravel()
+        cols = torch.full((Bn, N, nnz), -1, dtype=torch.int32, device=self.device)
+        wv = torch.zeros((Bn, N, nnz), dtype=torch.float64, device=self.device)
+        for b, (c, w) in enumerate(rows):
+            cols[b, :c.shape[0], :c.shape[1]] = c.to(self.device, torch.int32)
+            wv[b, :w.shape[0], :w.shape[1]] = w.to(self.device, torch.float64)
+        tri_d, vert_d, mass_d = (torch.as_tensor(x).to(self.device) for x in (tri_h, vert_h, mass_h))
+        t_d = torch.as_tensor(ts).to(self.device)
+        nv_d = torch.as_tensor(np.asarray(n_verts, np.int32)).to(self.device)
+        nbytes = int(self.lib.dm_heat_geodesic_bytes(Bn, N, nt))
+        if nbytes == 0:
+            raise ValueError(f"heat_geodesic_factor: meshes of up to 16384 vertices (got {N})")
+        buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        info = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_heat_geodesic_factor(self.ctx, Bn, N, nt, _ptr(tri_d), _ptr(vert_d), _ptr(cols), _ptr(wv), nnz, _ptr(mass_d),
+                                                   _ptr(t_d), _ptr(nv_d), _ptr(buf), _ptr(info)))
+        info_h = info.cpu().numpy()
+        for b in np.flatnonzero(info_h):
+            why = "; ".join(msg for bit, msg in self._GEOD_INFO if info_h[b] & bit)
+            raise ValueError(f"heat_geodesic_factor: mesh {b}: {why}")
+        return {"buf": buf, "B": Bn, "N": N, "nt": nt, "n_verts": n_verts, "t": ts}
+
+    def heat_geodesic(self, factors, sources=None, sym=False):
+        """Heat-method geodesic distances from the factors of heat_geodesic_factor (dm_heat_geodesic_solve): the reference's
+        heat_geodesic_from / heat_geodmat (geometry.py:587-740) for robust=False.
+        sources: None = all pairs; a 1-D list of vertex indices shared by every mesh; or one list per mesh (the same length, -1 = none).
+        Returns a device tensor D (B, N, ns) float64 with D[b, :, s] = the distances FROM sources[s] (a column of the reference's
+        matrix; rows past a mesh's vertex count are 0).  sym=True (all pairs only): (D + D^T) / 2 as the reference forms it
+        (trimesh.py:677-679).  A column's bits do not depend on the other sources or meshes of the call."""
+        import numpy as np
+        Bn, N = factors["B"], factors["N"]
+        nv = factors["n_verts"]
+        if sources is None:
+            src = np.full((Bn, N), -1, np.int32)
+            for b, n in enumerate(nv):
+                src[b, :n] = np.arange(n)
+        else:
+            if sym:
+                raise ValueError("heat_geodesic: sym=True needs all pairs (sources=None)")
+            src = np.asarray(sources)
+            src = np.broadcast_to(src, (Bn, src.shape[-1])) if src.ndim == 1 else src
+            if src.ndim != 2 or src.shape[0] != Bn or src.shape[1] == 0:
+                raise ValueError(f"heat_geodesic: sources must be (ns,) or ({Bn}, ns)")
+            for b, n in enumerate(nv):
+                if src[b].min() < -1 or src[b].max() >= n:
+                    raise ValueError(f"heat_geodesic: mesh {b}: source indices must lie in [0, {n})")
+            src = np.ascontiguousarray(src, np.int32)
+        ns = src.shape[1]
+        src_d = torch.as_tensor(src).to(self.device)
+        rows = torch.empty((Bn, ns, N), dtype=torch.float64, device=self.device)
+        info = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_heat_geodesic_solve(self.ctx, Bn, N, factors["nt"], _ptr(factors["buf"]), ns, _ptr(src_d), _ptr(rows),
+                                                  _ptr(info)))
+        bad = np.flatnonzero(info.cpu().numpy())
+        if len(bad):
+            raise ValueError(f"heat_geodesic: mesh {int(bad[0])}: a source lies outside [-1, n_verts)")
+        D = rows.transpose(1, 2)
+        if sym:
+            D = D * 0.5
+            D = D + D.transpose(1, 2)
+        return D.contiguous()
 
     def eigenbasis(self, W_list, mass, k, guard=None, degree=30, tol=1e-9, max_rounds=12, seed=0, ell=None):
         """k smallest eigenpairs of W phi = lambda A phi for a batch of meshes (reference TriMesh.process ->

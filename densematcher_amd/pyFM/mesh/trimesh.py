@@ -36,6 +36,8 @@ class TriMesh:
         self._L = None
         self.eigenvalues = None
         self.eigenvectors = None
+        self._edges = None
+        self._geod_factors = None        # device factors of the heat method (MatchEngine.heat_geodesic_factor), like the reference's _solver_heat / _solver_lap
         self.vertlist = args[0]
         self.facelist = args[1] if len(args) > 1 else None
 
@@ -53,6 +55,7 @@ class TriMesh:
             raise ValueError('Vertex list requires 3D coordinates')
         self._vertlist = vertlist.copy()
         self._W = self._W_dev = self._W_recipe = self._A = self._mass = self._L = self.eigenvalues = self.eigenvectors = None
+        self._geod_factors = None
 
     @property
     def facelist(self):
@@ -69,6 +72,8 @@ class TriMesh:
             self._facelist = facelist.astype(np.int64).copy()
         else:
             self._facelist = None
+        self._edges = None
+        self._geod_factors = None
 
     @property
     def W(self):
@@ -99,6 +104,7 @@ class TriMesh:
 
     @W.setter
     def W(self, value):
+        self._geod_factors = None
         self._W = value
         self._W_dev = None
         self._W_recipe = None
@@ -113,6 +119,7 @@ class TriMesh:
 
     @A.setter
     def A(self, value):
+        self._geod_factors = None
         self._A = value
         self._mass = None if value is None else np.asarray(value.diagonal())
 
@@ -262,6 +269,7 @@ class TriMesh:
         for b, mesh in enumerate(meshes):
             n = mesh.n_vertices
             mesh._W = None
+            mesh._geod_factors = None
             mesh._W_dev = (ell["cols"][b, :n], ell["w"][b, :n])
             mesh._W_recipe = "robust" if robust else "cotangent"
             mesh._A = None
@@ -376,6 +384,89 @@ class TriMesh:
             inds.append(newid)
             dists = np.minimum(dists, dist_from(newid))
         return np.asarray(inds)
+
+    # ------------------------------------------------------------- geodesic distances (reference trimesh.py:612-738)
+    @property
+    def edges(self):
+        """(p, 2) unique undirected edges (trimesh.py:236-247 -> geometry.edges_from_faces)"""
+        if self._edges is None:
+            from . import geometry
+            self._edges = geometry.edges_from_faces(self.facelist)
+        return self._edges
+
+    def _heat_time(self):
+        """t = (mean edge length)^2 (trimesh.py:661-665, 721-725)"""
+        edges = self.edges
+        v1 = self.vertlist[edges[:, 0]]
+        v2 = self.vertlist[edges[:, 1]]
+        return np.linalg.norm(v2 - v1, axis=1).mean() ** 2
+
+    def _has_laplacian(self):
+        return self._mass is not None and (self._W is not None or self._W_dev is not None or self._W_recipe is not None)
+
+    def _geod_operands(self):
+        """(verts, faces, W, mass) of MatchEngine.heat_geodesic_factor: the mesh's CURRENT W and A (the reference uses self.W /
+        self.A, whichever process built them); W as the device rows of the last assembly when they are still there"""
+        if not self._has_laplacian():
+            self.process(k=0)                                                    # trimesh.py:656-657
+        W = self._W_dev if (self._W is None and self._W_dev is not None) else self.W
+        if self._A is not None:                                                  # (an A set by the caller: diagonal only, like geometry's)
+            from . import geometry
+            geometry.lumped_mass(self._A)
+        return (self.vertlist, self.facelist, W, self._mass)
+
+    def _geodesic_factors(self):
+        if self._geod_factors is None:
+            from ...engine import default_engine
+            self._geod_factors = default_engine().heat_geodesic_factor([self._geod_operands()], self._heat_time())
+        return self._geod_factors
+
+    def release_geodesic_factors(self):
+        """free the device factors of the heat method (two N x N float64 matrices) that get_geodesic / geod_from keep on the mesh"""
+        self._geod_factors = None
+
+    def get_geodesic(self, dijkstra=False, robust=True, save=False, force_compute=False, sym=False, batch_size=500, verbose=False):
+        """(n, n) geodesic distance matrix, column j = distances from vertex j (trimesh.py:612-692).  dijkstra=True: shortest paths
+        along the edges (host).  robust=False: the reference's heat method on the mesh's W and A, on the device; the factors stay
+        on the mesh for geod_from (release_geodesic_factors frees them).  robust=True needs the potpourri3d wheel (ImportError).
+        save: mesh files are not handled here (the reference's ValueError('No path specified')); force_compute: there is no file
+        cache to bypass; batch_size: accepted, the result does not depend on it."""
+        if save:
+            raise ValueError('No path specified')
+        from . import geometry
+        if dijkstra:
+            return geometry.geodesic_distmat_dijkstra(self.vertlist, self.facelist)
+        if robust:                                                               # trimesh.py:670-671 (the wheel, or ImportError)
+            D = geometry.heat_geodmat_robust(self.vertlist, self.facelist, verbose=verbose)
+            if sym:
+                D *= .5
+                D += D.T
+            return D
+        from ...engine import default_engine
+        return default_engine().heat_geodesic(self._geodesic_factors(), sym=sym)[0].cpu().numpy()
+
+    def geod_from(self, i, robust=True):
+        """(n,) heat-method distances from vertex i (trimesh.py:694-738), with the factors cached on the mesh"""
+        if robust:                                                               # trimesh.py:700-705 (the wheel, or ImportError)
+            from . import geometry
+            return geometry._pp3d().MeshHeatMethodDistanceSolver(self.vertlist, self.facelist).compute_distance(i)
+        from ...engine import default_engine
+        from . import geometry
+        src = geometry._source_indices(int(i), self.n_vertices)                # (i = -1: the last vertex, as NumPy indexes it)
+        return default_engine().heat_geodesic(self._geodesic_factors(), src)[0, :, 0].cpu().numpy()
+
+    @staticmethod
+    def get_geodesic_many(meshes, dijkstra=False, robust=True, sym=False, verbose=False):
+        """mesh.get_geodesic(...) for several meshes: ONE factorisation and ONE solve for the batch (meshes padded to the largest;
+        each mesh's matrix is bit-identical to its own get_geodesic).  The batch's factors are freed on return (they are not
+        cached on the meshes).  Returns a list of (n_b, n_b) arrays."""
+        if dijkstra or robust:
+            return [mesh.get_geodesic(dijkstra=dijkstra, robust=robust, sym=sym, verbose=verbose) for mesh in meshes]
+        from ...engine import default_engine
+        eng = default_engine()
+        fac = eng.heat_geodesic_factor([mesh._geod_operands() for mesh in meshes], [mesh._heat_time() for mesh in meshes])
+        D = eng.heat_geodesic(fac, sym=sym).cpu().numpy()
+        return [np.ascontiguousarray(D[b, :mesh.n_vertices, :mesh.n_vertices]) for b, mesh in enumerate(meshes)]
 
     # ------------------------------------------------------------- spectral helpers
     def project(self, func, k=None):

@@ -404,6 +404,33 @@ int dm_laplacian_rows(dm_ctx* ctx, int B, int N, int nt, const int32_t* tri, con
 int dm_laplacian_ell(dm_ctx* ctx, int B, int N, int nt, const void* rows, int nnz, const int32_t* n_verts /*nullable*/,
                      int32_t* ell_cols, double* ell_vals, float* mass32, double* w_vals /*nullable*/, double* mass64 /*nullable*/);
 
+/* ---- heat-method geodesic distances ------------------------------------------------
+ * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
+ * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors
+ * A + tW and W (sparse.linalg.factorized) and solves for the sources.  Here, for B meshes padded to N vertices (n_verts, nullable:
+ * the real count of each; triangles (-1,-1,-1) pad tri), both systems are assembled dense and factored once (blocked Cholesky in
+ * float64, W grounded at vertex 0: row and column 0 replaced by the identity), then solved for any set of sources.
+ *   dm_heat_geodesic_bytes   device memory of the factors of B meshes (0 for an invalid size; N <= 16384).
+ *   dm_heat_geodesic_factor  tri (B,nt,3) int32, verts (B,N,3) fp64, the stiffness rows of W in ELL (ell_cols (B,N,nnz) int32,
+ *                            w_vals (B,N,nnz) fp64: what dm_laplacian_ell writes as w_vals, or rows of a host W; entries outside
+ *                            [0, n_verts) must be 0), mass64 (B,N) = diag A, t (B) the heat time of each mesh (trimesh.py:661-665:
+ *                            the squared mean edge length).  info (B): 0 ok, else a sum of 1 (A + tW not positive definite), 2 (W not
+ *                            positive definite once grounded: more than one connected component), 4 (a face of zero area), 8 (a face
+ *                            index or a W column outside [0, n_verts)), 16 (a vertex that no face references).  mass64 must be
+ *                            one third of the adjacent face areas (the cotangent lumped mass): only then does A div h lie in W's
+ *                            range, so that grounding W changes nothing but the constant the min-shift removes (not checked here:
+ *                            the Python layer refuses other masses).
+ *   dm_heat_geodesic_solve   D (B,ns,N) fp64: row s of mesh b = the distances FROM vertex sources[b][s] (geometry.py:660-668: phi of
+ *                            the heat method minus its minimum, 0 at the source; column j of the reference's matrix); sources (B,ns)
+ *                            int32 device, -1 = no source (a row of zeros).  A row's bits do not depend on the other sources or meshes
+ *                            of the call.  info (B): 1 if a source lies outside [-1, n_verts).  Work space: 2 B ns ceil64(N) doubles. */
+size_t dm_heat_geodesic_bytes(int B, int N, int nt);
+int dm_heat_geodesic_factor(dm_ctx* ctx, int B, int N, int nt, const int32_t* tri, const double* verts, const int32_t* ell_cols,
+                            const double* w_vals, int nnz, const double* mass64, const double* t, const int32_t* n_verts /*nullable*/,
+                            void* factors, int32_t* info);
+int dm_heat_geodesic_solve(dm_ctx* ctx, int B, int N, int nt, const void* factors, int ns, const int32_t* sources, double* D,
+                           int32_t* info);
+
 /* ---- precise (barycentric) map ----------------------------------------------------
  * For every vertex i of mesh 2 the face of mesh 1 its spectral embedding projects onto and the barycentric coordinates
  * of the projection: face_match (B,N2) int32, bary (B,N2,3) fp64; dense (B,N2,N1) fp64 optional = the same map as a
