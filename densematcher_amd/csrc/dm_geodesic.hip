@@ -524,6 +524,35 @@ int geod_subst(dm_ctx* ctx, const geod_layout& g, int ns, int z0, const double* 
 }
 }  // namespace
 
+namespace {
+// the solve on buffers the caller took: X, R = B ns Np doubles each; info is accumulated into (not cleared)
+int geod_solve_core(dm_ctx* ctx, const geod_layout& g, const void* factors, int ns, const int32_t* sources, double* D, double* X, double* R,
+                    int32_t* info) {
+    const int B = g.B, N = g.N, nt = g.nt, Np = g.Np;
+    const char* f = (const char*)factors;
+    const double* mat = (const double*)(f + g.mat);
+    const double* dinv = (const double*)(f + g.dinv);
+    const double* dinvt = (const double*)(f + g.dinvt);
+    const int32_t* hdr = (const int32_t*)(f + g.hdr);
+    DM_LAUNCH(ctx, "geod_rhs", geod_rhs_kernel, dim3(dm_cdiv(Np, 256), ns, B), dim3(256), 0, Np, ns, sources, hdr, X, info);
+    int rc = geod_subst(ctx, g, ns, 0, mat, dinv, dinvt, X, sources);
+    if (rc != DM_OK) return rc;
+    DM_LAUNCH(ctx, "geod_graddiv", geod_graddiv_kernel, dim3(dm_cdiv(Np, 256), ns, B), dim3(256), 0, nt, Np, ns, (const double*)X, R,
+              (const int32_t*)(f + g.tri), (const double*)(f + g.geom), (const int32_t*)(f + g.off), (const int32_t*)(f + g.list),
+              (const double*)(f + g.va), (const double*)(f + g.mass), hdr);
+    rc = geod_subst(ctx, g, ns, B, mat, dinv, dinvt, R, nullptr);
+    if (rc != DM_OK) return rc;
+    DM_LAUNCH(ctx, "geod_finish", geod_finish_kernel, dim3(ns, B), dim3(256), 0, N, Np, ns, (const double*)R, sources, hdr, D);
+    return DM_OK;
+}
+
+// sources of the all-pairs solve: src[b][i] = i for i < n_verts[b], else -1
+__global__ __launch_bounds__(256) void geod_iota_kernel(int N, const int32_t* __restrict__ hdr, int32_t* __restrict__ src) {
+    const int i = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y;
+    if (i < N) src[(size_t)b * N + i] = i < hdr[4 * b] ? i : -1;
+}
+}  // namespace
+
 extern "C" int dm_heat_geodesic_solve(dm_ctx* ctx, int B, int N, int nt, const void* factors, int ns, const int32_t* sources, double* D,
                                       int32_t* info) {
     if (!ctx) return DM_EINVAL;
@@ -532,26 +561,70 @@ extern "C" int dm_heat_geodesic_solve(dm_ctx* ctx, int B, int N, int nt, const v
     DM_REQUIRE(ctx, factors && sources && D && info, "null pointer");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const geod_layout g(B, N, nt);
-    const char* f = (const char*)factors;
-    const double* mat = (const double*)(f + g.mat);
-    const double* dinv = (const double*)(f + g.dinv);
-    const double* dinvt = (const double*)(f + g.dinvt);
-    const int Np = g.Np;
-    const size_t xb = (size_t)B * ns * Np * 8;
+    const size_t xb = (size_t)B * ns * g.Np * 8;
     int rc = dm_ws_reserve(ctx, 2 * dm_align_up(xb));
     if (rc != DM_OK) return rc;
     double* X = (double*)dm_ws_take(ctx, xb);
     double* R = (double*)dm_ws_take(ctx, xb);
-    const int32_t* hdr = (const int32_t*)(f + g.hdr);
     DM_CHECK_HIP(ctx, hipMemsetAsync(info, 0, (size_t)B * 4, ctx->stream));
-    DM_LAUNCH(ctx, "geod_rhs", geod_rhs_kernel, dim3(dm_cdiv(Np, 256), ns, B), dim3(256), 0, Np, ns, sources, hdr, X, info);
-    rc = geod_subst(ctx, g, ns, 0, mat, dinv, dinvt, X, sources);
+    return geod_solve_core(ctx, g, factors, ns, sources, D, X, R, info);
+}
+
+// ---- farthest-point sampling on heat-method distances (TriMesh.extract_fps(geodesic=True, robust=False)) ----------------------------
+// d(i) = row i of dm_heat_geodesic_solve = the distances FROM vertex i.  Route (a): the all-pairs rows once (B N^2 doubles + the solve's
+// 2 B N Np), then ONE sampling launch (dm_fps.hip: fps_rows).  Route (b), where that does not fit (or "fps_heat_route" = 2): per sample
+// one single-source solve whose source the previous step left in device memory, and one small kernel that folds the row in and
+// writes the next source.  A row's bits do not depend on the other sources of its solve, so both routes return the same indices.
+int dm_fps_rows(dm_ctx* ctx, int B, int N, const double* D, long long strideD, int ldd, const int32_t* nv4, int size, const int32_t* start,
+                int32_t* out, int32_t* info);
+int dm_fps_step_init(dm_ctx* ctx, int B, int N, const int32_t* nv4, int size, const int32_t* start, double* dists, int32_t* cur, int32_t* out,
+                     int32_t* info);
+int dm_fps_step(dm_ctx* ctx, int B, int N, const double* drow, const int32_t* nv4, int size, int s, double* dists, int32_t* cur, int32_t* out,
+                int32_t* info);
+
+extern "C" int dm_fps_heat(dm_ctx* ctx, int B, int N, int nt, const void* factors, int size, const int32_t* start, int32_t* out, int32_t* info) {
+    if (!ctx) return DM_EINVAL;
+    DM_REQUIRE(ctx, B > 0 && N > 0 && nt > 0 && size > 0 && B <= 32767, "sizes must be positive, B <= 32767");
+    DM_REQUIRE(ctx, N <= GEOD_MAXN, "N <= 16384");
+    DM_REQUIRE(ctx, factors && start && out && info, "null pointer");
+    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    const geod_layout g(B, N, nt);
+    const int32_t* hdr = (const int32_t*)((const char*)factors + g.hdr);
+    const size_t all = dm_align_up((size_t)B * N * N * 8) + 2 * dm_align_up((size_t)B * N * g.Np * 8) + dm_align_up((size_t)B * N * 4);
+    size_t free_b = 0, total_b = 0;
+    DM_CHECK_HIP(ctx, hipMemGetInfo(&free_b, &total_b));
+    // the all-pairs route while its work space fits what the context already holds plus half of the free device memory, and N <= 65535
+    const bool fits = N <= 65535 && all <= ctx->ws_bytes + free_b / 2;
+    const bool route_a = ctx->opt_fps_heat_route == 1 || (ctx->opt_fps_heat_route != 2 && fits);
+    DM_CHECK_HIP(ctx, hipMemsetAsync(info, 0, (size_t)B * 4, ctx->stream));
+    if (route_a) {
+        int rc = dm_ws_reserve(ctx, all);
+        if (rc != DM_OK) return rc;
+        double* D = (double*)dm_ws_take(ctx, (size_t)B * N * N * 8);
+        double* X = (double*)dm_ws_take(ctx, (size_t)B * N * g.Np * 8);
+        double* R = (double*)dm_ws_take(ctx, (size_t)B * N * g.Np * 8);
+        int32_t* src = (int32_t*)dm_ws_take(ctx, (size_t)B * N * 4);
+        if (!D || !X || !R || !src) return dm_fail(ctx, DM_ENOMEM, "fps_heat: workspace not reserved");
+        DM_LAUNCH(ctx, "geod_iota", geod_iota_kernel, dim3(dm_cdiv(N, 256), B), dim3(256), 0, N, hdr, src);
+        rc = geod_solve_core(ctx, g, factors, N, src, D, X, R, info);
+        if (rc != DM_OK) return rc;
+        return dm_fps_rows(ctx, B, N, D, (long long)N * N, N, hdr, size, start, out, info);
+    }
+    int rc = dm_ws_reserve(ctx, dm_align_up((size_t)B * N * 8) * 2 + 2 * dm_align_up((size_t)B * g.Np * 8) + dm_align_up((size_t)B * 4));
     if (rc != DM_OK) return rc;
-    DM_LAUNCH(ctx, "geod_graddiv", geod_graddiv_kernel, dim3(dm_cdiv(Np, 256), ns, B), dim3(256), 0, nt, Np, ns, (const double*)X, R,
-              (const int32_t*)(f + g.tri), (const double*)(f + g.geom), (const int32_t*)(f + g.off), (const int32_t*)(f + g.list),
-              (const double*)(f + g.va), (const double*)(f + g.mass), hdr);
-    rc = geod_subst(ctx, g, ns, B, mat, dinv, dinvt, R, nullptr);
+    double* dists = (double*)dm_ws_take(ctx, (size_t)B * N * 8);
+    double* drow = (double*)dm_ws_take(ctx, (size_t)B * N * 8);
+    double* X = (double*)dm_ws_take(ctx, (size_t)B * g.Np * 8);
+    double* R = (double*)dm_ws_take(ctx, (size_t)B * g.Np * 8);
+    int32_t* cur = (int32_t*)dm_ws_take(ctx, (size_t)B * 4);
+    if (!dists || !drow || !X || !R || !cur) return dm_fail(ctx, DM_ENOMEM, "fps_heat: workspace not reserved");
+    rc = dm_fps_step_init(ctx, B, N, hdr, size, start, dists, cur, out, info);
     if (rc != DM_OK) return rc;
-    DM_LAUNCH(ctx, "geod_finish", geod_finish_kernel, dim3(ns, B), dim3(256), 0, N, Np, ns, (const double*)R, sources, hdr, D);
+    for (int s = 0; s + 1 < size; ++s) {
+        rc = geod_solve_core(ctx, g, factors, 1, cur, drow, X, R, info);
+        if (rc != DM_OK) return rc;
+        rc = dm_fps_step(ctx, B, N, drow, hdr, size, s, dists, cur, out, info);
+        if (rc != DM_OK) return rc;
+    }
     return DM_OK;
 }

@@ -57,6 +57,9 @@ struct dm_ctx {
     int opt_p2pfm_direct = 1;    // 0: p2p_to_FM on the LDS-staged 64 x 64 tile kernel with split-K partials + a reduce launch
     int opt_simnn1_wt = 4;       // the biased-key search of the fused ZoomOut iteration: 4 = 8 waves, 256 x 256 tiles, one workgroup per CU; 2 = 4 waves, 128 x 256, two per CU
     int opt_zoomout_fused = 1;   // 0: ZoomOut as six launches per iteration (embedding, row build, search, merge, exact, p2p_to_FM [+ reduce])
+    int opt_zoomout_sub_fused = 1;   // the Python layer's choice for subsampled ZoomOut: 1 = dm_zoomout_sub (one device loop), 0 = the host-chained
+                                 // search + dm_p2p_to_fm_lstsq per iteration; the library only keeps the value
+    int opt_fps_heat_route = 0;  // dm_fps_heat: 0 = the all-pairs rows when their work space fits, else one solve per sample; 1 / 2 force a route
     int opt_energy_keep_gram = 0;  // 1: dm_fmap_energy_grad keeps P = A A^T, Q = B A^T of its FIRST call and reuses them while A, B
                                    // (pointers and sizes) stay the same: the caller promises not to change their contents (the L-BFGS
                                    // driver: the projected descriptors are fixed during a fit).  Setting the option again drops them.
@@ -289,6 +292,27 @@ size_t dm_p2pfm_ws_bytes(int B, int N2, int k1, int k2);
 size_t dm_p2pfm_xs_bytes(int B, int N2, int k2);
 template <typename TR>
 int dm_p2pfm_prescale(dm_ctx* ctx, int B, int N2, int k2, const TR* Phi2, int ld2, const double* mass2, double* Xs);
+
+// subsampled ZoomOut (dm_zoomsub.hip): what the loops of dm_zoomout.hip need besides their own state.  The caller fills N1, N2 (vertex
+// counts of the full meshes), sub1 (B, n1s), sub2 (B, n2s) and info (B, zeroed); dm_zo_sub_setup -- called after the arena has been
+// reserved with dm_zo_sub_ws_bytes on top of the loop's own need -- gathers the sampled rows (Kpad columns, row stride Kpad), forms
+// and factors the Gram matrix once and fills the rest.
+struct dm_zo_sub {
+    int N1 = 0, N2 = 0;
+    const int32_t* sub1 = nullptr; const int32_t* sub2 = nullptr;
+    int32_t* info = nullptr;                     // bit 1: Gram matrix not positive definite, bit 2: a sample index outside its mesh
+    double* Lf = nullptr; double* Lb = nullptr;  // (B, nslots, 256) each: the Cholesky factor's blocks and the inverses of its diagonal blocks as
+    int nslots = 0;                              // the operands of the forward / back substitution (dm_zoomsub.hip: zo_sub_pack_kernel)
+    double* R = nullptr;                         // (B, Kpad, Kpad) zeroed: right-hand side Phi2s^T Phi1s[p21] of the current iteration
+    const double* ones = nullptr;                // (B, n2s) unit "mass"
+    int Kpad = 0;
+};
+size_t dm_zo_sub_ws_bytes(int B, int n1s, int n2s, int kf, int real_bytes);
+template <typename TR>
+int dm_zo_sub_setup(dm_ctx* ctx, int B, int n1s, int n2s, int kf, const TR* Phi1, int ld1, const TR* Phi2, int ld2, dm_zo_sub* s,
+                    const TR** Phi1s, const TR** Phi2s);
+// C[b][:k, :k] = (L_k L_k^T)^-1 R[b][:k, :k] (leading blocks of the one factor), one launch
+int dm_zo_sub_solve(dm_ctx* ctx, int B, int k, const dm_zo_sub& s, double* C, int ldc, long long strideC);
 
 // dm_fmap_c00: sign(Phi1[0,0] Phi2[0,0]) sqrt(area2 / area1) per pair (pyFM/functional.py:654-658).  One workgroup of 256
 // threads per pair; also run as an extra workgroup of a projection's maxima pass (dm_fmap_fit), same arithmetic.

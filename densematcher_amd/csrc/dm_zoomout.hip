@@ -390,7 +390,7 @@ constexpr int ZO_NCH = 32;
 
 template <typename TR>
 static int zoomout_fused(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int step, const TR* Phi1, int ld1,
-                         const TR* Phi2, int ld2, const TR* mass2_in, const double* C0, double* Cout, int32_t* p21_out) {
+                         const TR* Phi2, int ld2, const TR* mass2_in, const double* C0, double* Cout, int32_t* p21_out, dm_zo_sub* sub) {
     const int kf = k0 + nit * step;
     const int Kpad = pad_to(kf, 16), R1 = pad_to(N1, 256), R2 = pad_to(N2, 256), N1pad = pad_to(N1, 128);
     const int ldT = zo_depth(kf), ldS = ldT;
@@ -401,14 +401,22 @@ static int zoomout_fused(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, in
     const size_t need = dm_align_up((size_t)B * N2 * 8) + dm_align_up(bytes_Fx) + dm_align_up(bytes_Fy) + 2 * dm_align_up(bytes_C) +
                         dm_align_up((size_t)B * R1 * 4) + dm_align_up((size_t)B * N1pad * 8) + dm_align_up((size_t)B * N1 * Kpad * 8) +
                         3 * dm_align_up((size_t)B * N2 * 4) + dm_align_up((size_t)B * ZO_NCH * 8) + dm_align_up(bytes_zero) +
-                        dm_simnn_ws_bytes(B, N2, N1, 0) + dm_p2pfm_ws_bytes(B, N2, kf, kf) + 65536;
+                        dm_simnn_ws_bytes(B, N2, N1, 0) + dm_p2pfm_ws_bytes(B, N2, kf, kf) + 65536 +
+                        (sub ? dm_zo_sub_ws_bytes(B, N1, N2, kf, (int)sizeof(TR)) : 0);
     // (dm_p2pfm_ws_bytes = the prescaled basis Xs AND the split-K partials of the staged p2p_to_FM, which dm_launch_p2p_to_fm falls back
     //  to beyond 15000 target vertices or with p2pfm_direct = 0: ADVICE r04 -- with the Xs share alone that fallback ran out of workspace)
     int rc = dm_ws_reserve(ctx, need);
     if (rc) return rc;
     const double* mass2 = nullptr;
-    rc = dm_widen_mass(ctx, (long long)B * N2, mass2_in, (double*)dm_ws_take(ctx, (size_t)B * N2 * 8), &mass2);
-    if (rc) return rc;
+    if (sub) {                                  // subsampled: the loop runs on the gathered rows (N1, N2 = sample counts), unit mass
+        rc = dm_zo_sub_setup<TR>(ctx, B, N1, N2, kf, Phi1, ld1, Phi2, ld2, sub, &Phi1, &Phi2);
+        if (rc) return rc;
+        ld1 = ld2 = sub->Kpad;
+        mass2 = sub->ones;
+    } else {
+        rc = dm_widen_mass(ctx, (long long)B * N2, mass2_in, (double*)dm_ws_take(ctx, (size_t)B * N2 * 8), &mass2);
+        if (rc) return rc;
+    }
     _Float16* Fx = (_Float16*)dm_ws_take(ctx, bytes_Fx);
     _Float16* Fy = (_Float16*)dm_ws_take(ctx, bytes_Fy);
     double* Ca = (double*)dm_ws_take(ctx, bytes_C);
@@ -499,8 +507,12 @@ static int zoomout_fused(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, in
         if (rc) return rc;
         if (last) break;
         const int kn = k + step;
-        rc = dm_launch_p2p_to_fm<TR>(ctx, B, N1, N2, kn, kn, p21, Phi1, ld1, Phi2, ld2, mass2, nxt, Kpad, (long long)Kpad * Kpad, Xs, Kpad);
+        rc = dm_launch_p2p_to_fm<TR>(ctx, B, N1, N2, kn, kn, p21, Phi1, ld1, Phi2, ld2, mass2, sub ? sub->R : nxt, Kpad, (long long)Kpad * Kpad, Xs, Kpad);
         if (rc) return rc;
+        if (sub) {                              // least squares: the leading block of the one Cholesky factor
+            rc = dm_zo_sub_solve(ctx, B, kn, *sub, nxt, Kpad, (long long)Kpad * Kpad);
+            if (rc) return rc;
+        }
         double* tmp = cur; cur = nxt; nxt = tmp;
         k = kn;
     }
@@ -510,15 +522,15 @@ static int zoomout_fused(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, in
 template <typename TR>
 static int zoomout_impl(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int step, const TR* Phi1, int ld1,
                         const TR* Phi2, int ld2, const TR* mass2_in, const double* C0, double* Cout,
-                        int32_t* p21_out) {
+                        int32_t* p21_out, dm_zo_sub* sub = nullptr) {
     if (!ctx) return DM_EINVAL;
     DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && k0 > 0 && nit >= 0 && step > 0, "sizes must be positive");
-    DM_REQUIRE(ctx, Phi1 && Phi2 && mass2_in && C0 && Cout, "null pointer");
+    DM_REQUIRE(ctx, Phi1 && Phi2 && (mass2_in || sub) && C0 && Cout, "null pointer");
     const int kf = k0 + nit * step;
     DM_REQUIRE(ctx, ld1 >= kf && ld2 >= kf, "not enough eigenvectors for k0 + nit*step (zoomout.py:87-92)");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (zoomout_fused_ok(ctx, N1, N2, kf))
-        return zoomout_fused<TR>(ctx, B, N1, N2, k0, nit, step, Phi1, ld1, Phi2, ld2, mass2_in, C0, Cout, p21_out);
+        return zoomout_fused<TR>(ctx, B, N1, N2, k0, nit, step, Phi1, ld1, Phi2, ld2, mass2_in, C0, Cout, p21_out, sub);
 
     const int N1pad = pad_to(N1, 128), N2pad = pad_to(N2, 128), Kpad = pad_to(kf, 16);
     const size_t bytes_AT = (size_t)B * Kpad * N2pad * 8, bytes_BT = (size_t)B * Kpad * N1pad * 8;
@@ -527,12 +539,19 @@ static int zoomout_impl(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int
                         dm_align_up((size_t)B * N1pad * 8) + dm_align_up((size_t)B * N2 * 4) +
                         dm_gred_ws_bytes(B, N2, N1) + dm_knn_split_prep_bytes(B, N2, kf) + dm_knn_split_ws_bytes(B, N2, N1, kf) +
                         dm_align_up((size_t)B * (N1pad / DM_EMB_COLS + 1) * 8) + dm_p2pfm_ws_bytes(B, N2, kf, kf) +
-                        dm_align_up((size_t)B * N2 * 8);
+                        dm_align_up((size_t)B * N2 * 8) + (sub ? dm_zo_sub_ws_bytes(B, N1, N2, kf, (int)sizeof(TR)) : 0);
     int rc = dm_ws_reserve(ctx, need);
     if (rc) return rc;
     const double* mass2 = nullptr;
-    rc = dm_widen_mass(ctx, (long long)B * N2, mass2_in, (double*)dm_ws_take(ctx, (size_t)B * N2 * 8), &mass2);
-    if (rc) return rc;
+    if (sub) {                                  // subsampled: the loop runs on the gathered rows (N1, N2 = sample counts), unit mass
+        rc = dm_zo_sub_setup<TR>(ctx, B, N1, N2, kf, Phi1, ld1, Phi2, ld2, sub, &Phi1, &Phi2);
+        if (rc) return rc;
+        ld1 = ld2 = sub->Kpad;
+        mass2 = sub->ones;
+    } else {
+        rc = dm_widen_mass(ctx, (long long)B * N2, mass2_in, (double*)dm_ws_take(ctx, (size_t)B * N2 * 8), &mass2);
+        if (rc) return rc;
+    }
     double* AT = (double*)dm_ws_take(ctx, bytes_AT);
     double* BT = (double*)dm_ws_take(ctx, bytes_BT);
     double* Ca = (double*)dm_ws_take(ctx, bytes_C);
@@ -574,7 +593,13 @@ static int zoomout_impl(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int
         if (rc) return rc;
         if (last) break;
         const int kn = k + step;
-        rc = dm_launch_p2p_to_fm<TR>(ctx, B, N1, N2, kn, kn, p21, Phi1, ld1, Phi2, ld2, mass2, nxt, kn, (long long)kn * kn);
+        if (sub) {
+            rc = dm_launch_p2p_to_fm<TR>(ctx, B, N1, N2, kn, kn, p21, Phi1, ld1, Phi2, ld2, mass2, sub->R, sub->Kpad, (long long)sub->Kpad * sub->Kpad);
+            if (rc) return rc;
+            rc = dm_zo_sub_solve(ctx, B, kn, *sub, nxt, kn, (long long)kn * kn);
+        } else {
+            rc = dm_launch_p2p_to_fm<TR>(ctx, B, N1, N2, kn, kn, p21, Phi1, ld1, Phi2, ld2, mass2, nxt, kn, (long long)kn * kn);
+        }
         if (rc) return rc;
         double* tmp = cur; cur = nxt; nxt = tmp;
         k = kn;
@@ -591,4 +616,43 @@ extern "C" int dm_zoomout_f64(dm_ctx* ctx, int B, int N1, int N2, int k0, int ni
                               const double* Phi2, int ld2, const double* mass2, const double* C0, double* Cout,
                               int32_t* p21_out) {
     return zoomout_impl<double>(ctx, B, N1, N2, k0, nit, step, Phi1, ld1, Phi2, ld2, mass2, C0, Cout, p21_out);
+}
+
+// ---- subsampled ZoomOut (zoomout.py:95-113 with subsample = (sub1, sub2)) --------------------------------------------------------------
+// The loops above on the sampled rows, with unit mass and the least-squares solve of dm_zoomsub.hip behind every product: the search
+// of an iteration is the fused one when both sample sets have at least 256 vertices and kf <= 208, the generic one otherwise.  Then
+// the final vertex map on ALL vertices (zoomout.py:111-113) by dm_fm_to_p2p, reading the map from Cout.
+static int zo_full_knn21(dm_ctx* ctx, int B, int N1, int N2, int k, const float* Phi1, int ld1, const float* Phi2, int ld2, const double* C, int32_t* p21) {
+    return dm_fm_to_p2p(ctx, B, N1, N2, k, k, Phi1, ld1, Phi2, ld2, nullptr, C, p21, nullptr, nullptr, nullptr);
+}
+static int zo_full_knn21(dm_ctx* ctx, int B, int N1, int N2, int k, const double* Phi1, int ld1, const double* Phi2, int ld2, const double* C, int32_t* p21) {
+    return dm_fm_to_p2p_f64(ctx, B, N1, N2, k, k, Phi1, ld1, Phi2, ld2, nullptr, C, p21, nullptr, nullptr, nullptr);
+}
+template <typename TR>
+static int zoomout_sub_impl(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, const int32_t* sub1, const int32_t* sub2, int k0, int nit,
+                            int step, const TR* Phi1, int ld1, const TR* Phi2, int ld2, const double* C0, double* Cout, int32_t* p21_out,
+                            int32_t* info) {
+    if (!ctx) return DM_EINVAL;
+    DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && n1s > 0 && n2s > 0 && k0 > 0 && nit >= 0 && step > 0, "sizes must be positive");
+    DM_REQUIRE(ctx, Phi1 && Phi2 && sub1 && sub2 && C0 && Cout && info, "null pointer");
+    const int kf = k0 + nit * step;
+    DM_REQUIRE(ctx, ld1 >= kf && ld2 >= kf, "not enough eigenvectors for k0 + nit*step (zoomout.py:87-92)");
+    DM_REQUIRE(ctx, kf <= 256, "the subsampled loop needs k0 + nit*step <= 256");
+    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    DM_CHECK_HIP(ctx, hipMemsetAsync(info, 0, (size_t)B * 4, ctx->stream));
+    dm_zo_sub sub;
+    sub.N1 = N1; sub.N2 = N2; sub.sub1 = sub1; sub.sub2 = sub2; sub.info = info;
+    int rc = zoomout_impl<TR>(ctx, B, n1s, n2s, k0, nit, step, Phi1, ld1, Phi2, ld2, (const TR*)nullptr, C0, Cout, nullptr, &sub);
+    if (rc || !p21_out) return rc;
+    return zo_full_knn21(ctx, B, N1, N2, kf, Phi1, ld1, Phi2, ld2, Cout, p21_out);
+}
+extern "C" int dm_zoomout_sub(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, const int32_t* sub1, const int32_t* sub2, int k0, int nit,
+                              int step, const float* Phi1, int ld1, const float* Phi2, int ld2, const double* C0, double* Cout,
+                              int32_t* p21_out, int32_t* info) {
+    return zoomout_sub_impl<float>(ctx, B, N1, N2, n1s, n2s, sub1, sub2, k0, nit, step, Phi1, ld1, Phi2, ld2, C0, Cout, p21_out, info);
+}
+extern "C" int dm_zoomout_sub_f64(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, const int32_t* sub1, const int32_t* sub2, int k0, int nit,
+                                  int step, const double* Phi1, int ld1, const double* Phi2, int ld2, const double* C0, double* Cout,
+                                  int32_t* p21_out, int32_t* info) {
+    return zoomout_sub_impl<double>(ctx, B, N1, N2, n1s, n2s, sub1, sub2, k0, nit, step, Phi1, ld1, Phi2, ld2, C0, Cout, p21_out, info);
 }

@@ -81,6 +81,7 @@ class MatchEngine:
         if rc != 0:
             raise _lib.DenseMatchError(f"dm_create failed with status {rc}: {self.lib.dm_last_error(None).decode()}")
         self.ctx = ctx
+        self._options = dict(self.OPTION_DEFAULTS)
 
     def close(self):
         if getattr(self, "ctx", None):
@@ -125,15 +126,23 @@ class MatchEngine:
         self.stream.synchronize()
 
     OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0, "energy_keep_gram": 0,
-                       "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1}
+                       "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
+                       "zoomout_sub_fused": 1, "fps_heat_route": 0}
 
     def set_option(self, name, value):
         """Choose between code paths of the library (include/densematch.h: dm_set_option).  Most settings return the same
         results bit for bit; "solve_pcg" (the batched iteration in front of the direct solvers) changes bits: its C agrees with
         solve_pcg = 0 to max(1e-9, 4 (n + D) u kappa) relative per system of condition number kappa (u = 2^-53,
         tests/test_gpu_solver_conditioning.py); "fit_f32" runs the fused fit's element loop in fp32 (the reference's precision) and
-        "fit_mfma" chooses the summation order of its products, so both change the fused fit's bits."""
+        "fit_mfma" chooses the summation order of its products, so both change the fused fit's bits; "zoomout_sub_fused" chooses
+        between the one-factor device loop of subsampled ZoomOut (1) and the host-chained least-squares steps (0): the maps agree
+        to 1e-9, not bit for bit."""
         self._chk(self.lib.dm_set_option(self.ctx, name.encode(), int(value)))
+        self._options[name] = int(value)
+
+    def get_option(self, name):
+        """the value set_option last gave `name` on this engine (its default otherwise)"""
+        return self._options[name]
 
     def reset_options(self):
         for k, v in self.OPTION_DEFAULTS.items():
@@ -752,6 +761,49 @@ class MatchEngine:
             D = D + D.transpose(1, 2)
         return D.contiguous()
 
+    # ------------------------------------------------------------- farthest-point sampling (dm_fps_*)
+    def fps(self, verts, size, start, n_verts=None):
+        """Farthest-point sampling on Euclidean distances (geometry.py:839-848 with the distance of trimesh.py:872-873), the
+        reference's indices.  verts (B,N,3) or (N,3) float64; start: one index or (B,); n_verts (B,) for padded batches.
+        Returns (B,size) int32 on the device."""
+        import numpy as np
+        verts = self._dev(verts, torch.float64, "verts")
+        if verts.dim() == 2:
+            verts = verts[None]
+        if verts.dim() != 3 or verts.shape[2] != 3:
+            raise ValueError("fps: verts must be (B,N,3)")
+        Bn, N = int(verts.shape[0]), int(verts.shape[1])
+        if N > 16384:
+            raise ValueError(f"fps: meshes of up to 16384 vertices (got {N})")
+        st = np.broadcast_to(np.asarray(start, np.int64), (Bn,))
+        nv = np.full((Bn,), N, np.int64) if n_verts is None else np.broadcast_to(np.asarray(n_verts, np.int64), (Bn,))
+        if nv.min() < 1 or nv.max() > N or st.min() < 0 or np.any(st >= nv):
+            raise ValueError("fps: start indices must lie in [0, n_verts), n_verts in [1, N]")
+        st_d = torch.as_tensor(np.ascontiguousarray(st, np.int32)).to(self.device)
+        nv_d = torch.as_tensor(np.ascontiguousarray(nv, np.int32)).to(self.device)
+        out = torch.empty((Bn, int(size)), dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_fps_euclid(self.ctx, Bn, N, _ptr(verts), _ptr(nv_d), int(size), _ptr(st_d), _ptr(out)))
+        return out
+
+    def fps_heat(self, factors, size, start):
+        """Farthest-point sampling on the heat-method distances of heat_geodesic_factor's factors: d(i) = geod_from(i, robust=False).
+        start: one index or one per mesh.  Returns (B,size) int32 on the device.  The whole sampling is one call without host
+        synchronisation ("fps_heat_route": all-pairs rows + one sampling launch, or one single-source solve per sample)."""
+        import numpy as np
+        Bn, N = factors["B"], factors["N"]
+        st = np.broadcast_to(np.asarray(start, np.int64), (Bn,))
+        for b, n in enumerate(factors["n_verts"]):
+            if st[b] < 0 or st[b] >= n:
+                raise ValueError(f"fps_heat: mesh {b}: the start vertex must lie in [0, {n})")
+        st_d = torch.as_tensor(np.ascontiguousarray(st, np.int32)).to(self.device)
+        out = torch.empty((Bn, int(size)), dtype=torch.int32, device=self.device)
+        info = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_fps_heat(self.ctx, Bn, N, factors["nt"], _ptr(factors["buf"]), int(size), _ptr(st_d), _ptr(out), _ptr(info)))
+        info_h = info.cpu().numpy()
+        for b in np.flatnonzero(info_h):
+            raise ValueError(f"fps_heat: mesh {int(b)}: " + ("a start vertex outside the mesh" if info_h[b] & 1 else "a distance that is not finite"))
+        return out
+
     def eigenbasis(self, W_list, mass, k, guard=None, degree=30, tol=1e-9, max_rounds=12, seed=0, ell=None):
         """k smallest eigenpairs of W phi = lambda A phi for a batch of meshes (reference TriMesh.process ->
         laplacian_spectrum: ARPACK on the host, one mesh at a time).
@@ -964,8 +1016,21 @@ class MatchEngine:
             raise _lib.DenseMatchError(f"least-squares map: Phi2^T Phi2 is not positive definite for pairs {bad.tolist()[:8]}")
         return Cm
 
-    def zoomout(self, Phi1, Phi2, a2, C0, nit, step=1, return_p2p=False):
-        sfx, Phi1, Phi2, a2 = self._reals(Phi1, Phi2, a2)
+    def _sub_indices(self, sub, B, name):
+        sub = self._dev(sub, torch.int32, name)
+        if sub.dim() == 1:
+            sub = sub[None].expand(B, -1).contiguous()
+        if sub.dim() != 2 or sub.shape[0] != B or sub.shape[1] == 0:
+            raise ValueError(f"zoomout: {name} must be (n,) or ({B}, n)")
+        return sub
+
+    def zoomout(self, Phi1, Phi2, a2, C0, nit, step=1, return_p2p=False, subsample=None):
+        """ZoomOut (dm_zoomout): C0 (B,k0,k0) -> (B,kf,kf), kf = k0 + nit*step [, knn21 of the result (B,N2)].
+        subsample = (sub1, sub2), index arrays (n,) shared by the batch or (B, n): the subsampled form (reference
+        zoomout_refine(subsample=...), dm_zoomout_sub): the iterations on Phi1[sub1], Phi2[sub2] with the least-squares map (a2 is
+        not used and may be None), the returned vertex map on all vertices.  Raises DenseMatchError where Phi2[sub2][:, :kf] has
+        no full column rank (fewer distinct samples than kf), ValueError for a sample index outside its mesh."""
+        sfx, Phi1, Phi2, a2 = self._reals(Phi1, Phi2, None if subsample is not None else a2)
         C0 = self._dev(C0, torch.float64, "C0")
         B, N1, ld1 = Phi1.shape
         _, N2, ld2 = Phi2.shape
@@ -977,6 +1042,22 @@ class MatchEngine:
         assert kf <= ld2, f"Not enough eigenvectors on target : {kf} are needed when {ld2} are provided"
         Cout = torch.empty((B, kf, kf), dtype=torch.float64, device=self.device)
         p21 = torch.empty((B, N2), dtype=torch.int32, device=self.device) if return_p2p else None
+        if subsample is not None:
+            sub1 = self._sub_indices(subsample[0], B, "sub1")
+            sub2 = self._sub_indices(subsample[1], B, "sub2")
+            info = torch.zeros((B,), dtype=torch.int32, device=self.device)
+            self._chk(getattr(self.lib, "dm_zoomout_sub" + sfx)(self.ctx, B, N1, N2, sub1.shape[1], sub2.shape[1], _ptr(sub1), _ptr(sub2),
+                                                               k0, nit, step, _ptr(Phi1), ld1, _ptr(Phi2), ld2, _ptr(C0), _ptr(Cout),
+                                                               _ptr(p21), _ptr(info)))
+            info_h = info.cpu()
+            bad = torch.nonzero(info_h & 2).flatten()
+            if bad.numel():
+                raise ValueError(f"zoomout: sample indices outside the mesh for pairs {bad.tolist()[:8]}")
+            bad = torch.nonzero(info_h & 1).flatten()
+            if bad.numel():
+                raise _lib.DenseMatchError(f"subsampled zoomout: Phi2[sub2]^T Phi2[sub2] is not positive definite for pairs {bad.tolist()[:8]} "
+                                           f"({sub2.shape[1]} samples for {kf} eigenvectors; duplicated samples?)")
+            return (Cout, p21) if return_p2p else Cout
         self._chk(getattr(self.lib, "dm_zoomout" + sfx)(self.ctx, B, N1, N2, k0, nit, step, _ptr(Phi1), ld1, _ptr(Phi2), ld2, _ptr(a2),
                                       _ptr(C0), _ptr(Cout), _ptr(p21)))
         return (Cout, p21) if return_p2p else Cout

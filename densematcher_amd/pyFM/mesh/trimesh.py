@@ -353,18 +353,34 @@ class TriMesh:
         return meshes
 
     # ------------------------------------------------------------- vertex sampling (input of the subsampled ZoomOut)
-    def extract_fps(self, size, random_init=True, geodesic=True, no_load=False, verbose=False, rng=None):
+    def extract_fps(self, size, random_init=True, geodesic=True, no_load=False, verbose=False, rng=None, robust=True, start=None):
         """Farthest point sampling (trimesh.py:847-893 -> geometry.py:813-845): start at a random vertex, then repeatedly
-        take the vertex farthest from the ones taken.  geodesic=False: Euclidean distances, the reference's arithmetic.
-        geodesic=True: the reference measures with the heat method of the external potpourri3d wheel (`geod_from`); here the
-        distance is the shortest path along mesh edges (Dijkstra on the edge graph) and a warning says so: the samples
-        spread the same way, they are not the same vertices.  `rng`: numpy Generator for the start vertex (the reference
-        draws from an unseeded one: its samples are not reproducible either).  Host code: it selects inputs of the path."""
-        rng = np.random.default_rng() if rng is None else rng
+        take the vertex farthest from the ones taken.
+        geodesic=False: Euclidean distances in the reference's arithmetic, on the device (dm_fps_euclid): the reference's indices.
+        geodesic=True, robust=False: the reference's own heat method (`geod_from(i, robust=False)`), on the device with the
+        factors cached on the mesh (dm_fps_heat).
+        geodesic=True, robust=True (the defaults): the reference measures with the heat method of the external potpourri3d wheel;
+        here the distance is the shortest path along mesh edges (Dijkstra on the edge graph, host) and a warning says so: the
+        samples spread the same way, they are not the same vertices.
+        `rng`: numpy Generator for the start vertex (the reference draws from an unseeded one: its samples are not reproducible
+        either); `start`: the first vertex itself."""
         n = self.n_vertices
+        if start is None:
+            rng = np.random.default_rng() if rng is None else rng
+            start = int(rng.integers(n))                                        # geometry.py:833
+        start = int(start)
+        if not 0 <= start < n:
+            raise ValueError(f"extract_fps: the start vertex must lie in [0, {n})")
         if not geodesic:
+            if n <= 16384:
+                from ...engine import default_engine
+                return default_engine().fps(np.ascontiguousarray(self.vertlist, dtype=np.float64)[None], size, start)[0].cpu().numpy().astype(np.int64)
+
             def dist_from(i):
                 return np.linalg.norm(self.vertlist - self.vertlist[i, None, :], axis=1)
+        elif not robust:
+            from ...engine import default_engine
+            return default_engine().fps_heat(self._geodesic_factors(), size, start)[0].cpu().numpy().astype(np.int64)
         else:
             import scipy.sparse.csgraph as csgraph
             warnings.warn("extract_fps(geodesic=True): potpourri3d's heat-method geodesics are not available; using shortest paths "
@@ -377,13 +393,41 @@ class TriMesh:
 
             def dist_from(i):
                 return csgraph.dijkstra(G, directed=False, indices=i)
-        inds = [int(rng.integers(n))]                                           # geometry.py:833
+        inds = [start]
         dists = dist_from(inds[0])
         for _ in range(size - 1):                                               # geometry.py:838-843
             newid = int(np.argmax(dists))
             inds.append(newid)
             dists = np.minimum(dists, dist_from(newid))
         return np.asarray(inds)
+
+    @staticmethod
+    def extract_fps_many(meshes, size, geodesic=True, robust=True, rng=None, starts=None):
+        """mesh.extract_fps(size, ...) for several meshes: ONE sampling call for the batch (meshes padded to the largest) and, for
+        the heat method, one factorisation; each mesh's samples equal its own extract_fps from the same start.  `starts`: one
+        first vertex per mesh, else drawn from `rng` mesh by mesh.  Returns a list of index arrays."""
+        meshes = list(meshes)
+        if starts is None:
+            rng = np.random.default_rng() if rng is None else rng
+            starts = [int(rng.integers(mesh.n_vertices)) for mesh in meshes]
+        starts = [int(s) for s in starts]
+        if len(starts) != len(meshes):
+            raise ValueError("extract_fps_many: one start per mesh")
+        nmax = max(mesh.n_vertices for mesh in meshes)
+        if (geodesic and robust) or nmax > 16384:
+            return [mesh.extract_fps(size, geodesic=geodesic, robust=robust, start=s) for mesh, s in zip(meshes, starts)]
+        from ...engine import default_engine
+        eng = default_engine()
+        if geodesic:
+            fac = eng.heat_geodesic_factor([mesh._geod_operands() for mesh in meshes], [mesh._heat_time() for mesh in meshes])
+            out = eng.fps_heat(fac, size, starts)
+        else:
+            V = np.zeros((len(meshes), nmax, 3), np.float64)
+            for b, mesh in enumerate(meshes):
+                V[b, :mesh.n_vertices] = mesh.vertlist
+            out = eng.fps(V, size, starts, n_verts=[mesh.n_vertices for mesh in meshes])
+        out = out.cpu().numpy().astype(np.int64)
+        return [out[b] for b in range(len(meshes))]
 
     # ------------------------------------------------------------- geodesic distances (reference trimesh.py:612-738)
     @property

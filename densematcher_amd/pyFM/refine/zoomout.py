@@ -1,7 +1,7 @@
 """
 ZoomOut with the reference's signatures (densematcher/pyFM/refine/zoomout.py), upstream-pyFM semantics for the
 FM -> p2p step (the fork's call at zoomout.py:40,112 is broken as shipped).
-The whole loop runs on the GPU without host synchronisation (dm_zoomout).
+The whole loop runs on the GPU without host synchronisation (dm_zoomout; on a vertex subsample dm_zoomout_sub).
 """
 import numpy as np
 
@@ -76,10 +76,23 @@ def zoomout_refine(FM_12, evects1, evects2, nit=10, step=1, A2=None, subsample=N
         f"Not enough eigenvectors on target : {k2_0 + nit * step2} are needed when {evects2.shape[1]} are provided"
     if subsample is not None:
         sub1, sub2 = subsample
+        from ...engine import default_engine
+        eng = default_engine()
+        if step1 == step2 and k1_0 == k2_0 and k1_0 + nit * step1 <= 256 and eng.get_option("zoomout_sub_fused"):
+            # square map, one step size: one device loop on one Cholesky factor of Phi2[sub2]^T Phi2[sub2] (dm_zoomout_sub)
+            from ..spectral.convert import _basis, _real_dtype
+            dt = _real_dtype(evects1, evects2)
+            kf = k1_0 + nit * step1
+            sub = (np.ascontiguousarray(sub1, dtype=np.int32), np.ascontiguousarray(sub2, dtype=np.int32))
+            res = eng.zoomout(_basis(evects1, kf, dt), _basis(evects2, kf, dt), None, np.ascontiguousarray(FM_12, dtype=np.float64)[None],
+                              nit, step1, return_p2p=return_p2p, subsample=sub)
+            if return_p2p:
+                return res[0][0].cpu().numpy(), res[1][0].cpu().numpy().astype(np.int64)
+            return res[0].cpu().numpy()
+        # rectangular maps, two step sizes, or "zoomout_sub_fused" = 0: the search and the least-squares map chained from the host
         FM = _run(FM_12, np.asarray(evects1)[sub1], np.asarray(evects2)[sub2], nit, step, None, False)
         if return_p2p:
-            from ...engine import default_engine
-            return FM, _knn21(default_engine(), FM, evects1, evects2)[0].cpu().numpy().astype(np.int64)
+            return FM, _knn21(eng, FM, evects1, evects2)[0].cpu().numpy().astype(np.int64)
         return FM
     return _run(FM_12, evects1, evects2, nit, step, A2, return_p2p)
 
@@ -96,9 +109,14 @@ def mesh_zoomout_refine(FM_12, mesh1, mesh2, nit=10, step=1, subsample=None, ret
 
 def mesh_zoomout_refine_p2p(p2p_21, mesh1, mesh2, k_init, nit=10, step=1, subsample=None, return_p2p=False, n_jobs=1,
                             p2p_on_sub=False, verbose=False):
-    """reference zoomout.py:164-217"""
-    if subsample is not None or p2p_on_sub:
-        raise NotImplementedError("farthest-point subsampling is outside the matching path")
-    FM_12_init = spectral.mesh_p2p_to_FM(p2p_21, mesh1, mesh2, dims=k_init, subsample=None)
-    return zoomout_refine(FM_12_init, mesh1.eigenvectors, mesh2.eigenvectors, nit, step=step, A2=mesh2.A,
+    """reference zoomout.py:164-217.  p2p_on_sub: p2p_21 maps the samples of mesh2 to the samples of mesh1 (indices into sub1),
+    the initial map is then the least-squares one on the sampled rows (:208-209)."""
+    if np.issubdtype(type(subsample), np.integer):                              # zoomout.py:199-206
+        if p2p_on_sub:
+            raise ValueError("P2P can't be defined on undefined subsample")
+        if verbose:
+            print(f'Computing farthest point sampling of size {subsample}')
+        subsample = (mesh1.extract_fps(subsample), mesh2.extract_fps(subsample))
+    FM_12_init = spectral.mesh_p2p_to_FM(p2p_21, mesh1, mesh2, dims=k_init, subsample=subsample if p2p_on_sub else None)
+    return zoomout_refine(FM_12_init, mesh1.eigenvectors, mesh2.eigenvectors, nit, step=step, A2=mesh2.A, subsample=subsample,
                           return_p2p=return_p2p, n_jobs=n_jobs, verbose=verbose)

@@ -83,6 +83,11 @@ size_t dm_workspace_bytes(const dm_ctx* ctx);
  *                           passed; the caller promises not to change their CONTENTS meanwhile (an optimiser's evaluations of one fit).  Setting the option (to any value) drops what is kept.
  *   "zoomout_fused" 1 | 0   dm_zoomout on meshes of at least 256 vertices, maps up to 208: five launches per iteration (embedding + split
  *                           rows, biased-key search, merge, exact, p2p_to_FM) | six (seven with the reduce) through K-major copies
+ *   "zoomout_sub_fused" 1 | 0   subsampled ZoomOut in the Python layer (refine.zoomout_refine(subsample=...), square map, one step size):
+ *                           dm_zoomout_sub, one device loop on one Cholesky factor | the host-chained search + dm_p2p_to_fm_lstsq per
+ *                           iteration.  The library only keeps the value.  The two settings agree to 1e-9, not bit for bit.
+ *   "fps_heat_route" 0 | 1 | 2   dm_fps_heat: the all-pairs rows when their work space fits, else one solve per sample | always the
+ *                           all-pairs rows | always one solve per sample.  Same indices.
  *   "p2pfm_direct"  1 | 0   dm_p2p_to_fm (and the p2p_to_FM steps of dm_zoomout / dm_icp): register-resident tiles, operands straight
  *                           from global memory, fixed-order in-workgroup reduction | LDS-staged 64 x 64 tiles + split-K partials + reduce
  *   "simnn1_wt"     4 | 2   tile shape of the fused ZoomOut search: 8 waves, 256 x 256 | 4 waves, 128 x 256 (two workgroups per CU)
@@ -483,6 +488,37 @@ int dm_zoomout(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int step,
 int dm_zoomout_f64(dm_ctx* ctx, int B, int N1, int N2, int k0, int nit, int step,
                    const double* Phi1, int ld1, const double* Phi2, int ld2,
                    const double* mass2, const double* C0, double* Cout, int32_t* p21_out /*nullable*/);
+
+/* ---- subsampled ("fast") ZoomOut --------------------------------------------------
+ * zoomout.py:95-113 with subsample = (sub1, sub2): the nit iterations run on the rows Phi1[sub1] (n1s), Phi2[sub2] (n2s) with the
+ * least-squares p2p_to_FM (no mass, convert.py:51); p21_out (B,N2) optional = knn21(Cout) on ALL vertices (zoomout.py:111-113).
+ * sub1 (B,n1s), sub2 (B,n2s) int32 device.  Square map, one step size; kf = k0 + nit*step <= 256.  One device loop without host
+ * synchronisation: the rows are gathered and the Gram matrix Phi2s[:, :kf]^T Phi2s[:, :kf] is formed and Cholesky-factored ONCE (the
+ * factor of a leading block is the leading block of the factor), every iteration then costs the search of dm_zoomout on the
+ * samples, one product and one triangular-solve launch.  info (B): 0 ok, else a sum of 1 (the Gram matrix is not positive definite
+ * to 1e-10 of its diagonal: fewer distinct samples than kf, cond(Phi2s) beyond 1e5) and 2 (a sample index outside its mesh; it is
+ * clamped, nothing reads outside its arrays).  The results of a flagged pair are meaningless.  A pair's result does not depend on
+ * the other pairs of the call. */
+int dm_zoomout_sub(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, const int32_t* sub1, const int32_t* sub2,
+                   int k0, int nit, int step, const float* Phi1, int ld1, const float* Phi2, int ld2,
+                   const double* C0, double* Cout, int32_t* p21_out /*nullable*/, int32_t* info);
+int dm_zoomout_sub_f64(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, const int32_t* sub1, const int32_t* sub2,
+                       int k0, int nit, int step, const double* Phi1, int ld1, const double* Phi2, int ld2,
+                       const double* C0, double* Cout, int32_t* p21_out /*nullable*/, int32_t* info);
+
+/* ---- farthest-point sampling --------------------------------------------------------
+ * geometry.py:839-848 (behind TriMesh.extract_fps): out[b][0] = start[b], dists = d(start); size - 1 times new = argmax(dists) (the
+ * LOWEST index among equal maxima, like np.argmax), dists = min(dists, d(new)).  out (B,size) int32; vertices >= n_verts[b] are
+ * never chosen; with size > n_verts the indices repeat as the reference's do (all distances 0 -> vertex 0).  The whole loop of a
+ * mesh runs on the device without host synchronisation, a batch is one call.  N <= 16384.
+ *   dm_fps_euclid  d(i) = |V - V[i]| as np.linalg.norm(V - V[i], axis=1) rounds it: sqrt((dx dx + dy dy) + dz dz) in float64 without
+ *                  fused multiply-add, correctly rounded square root: the reference's indices.  verts (B,N,3); start is clamped
+ *                  into the mesh.
+ *   dm_fps_heat    d(i) = row i of dm_heat_geodesic_solve for these factors (TriMesh.geod_from(i, robust=False)); info (B): 1 a
+ *                  start outside [0, n_verts), 2 a distance that is not finite. */
+int dm_fps_euclid(dm_ctx* ctx, int B, int N, const double* verts, const int32_t* n_verts /*nullable*/, int size,
+                  const int32_t* start, int32_t* out);
+int dm_fps_heat(dm_ctx* ctx, int B, int N, int nt, const void* factors, int size, const int32_t* start, int32_t* out, int32_t* info);
 
 /* ---- spectral ICP -------------------------------------------------------------
  * nit times: p21 = knn21(C); Chat = argmin |Phi2[:, :k2] X - Phi1[p21, :k1]|_F (no mass);
