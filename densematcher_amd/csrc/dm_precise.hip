@@ -241,7 +241,9 @@ __global__ __launch_bounds__(256) void precise_project_kernel(const double* __re
             const double* cst = fc + ((long long)b * nf + f) * 4;
             double s_, t_, sq;
             point_triangle(cst[0], cst[1], cst[2], d, e, ff, multi, s_, t_, sq);
-            const double dd = sqrt(fmax(sq, 0.0));
+            // (not fmax(sq, 0): that turns the NaN of a zero-area face (region 0: 0 * inf) into distance 0, the face then wins with NaN
+            //  weights.  A NaN distance loses every comparison below: such a candidate is passed over.)
+            const double dd = sqrt(sq < 0.0 ? 0.0 : sq);
             if (dd < bd || (dd == bd && f < bf)) { bd = dd; bf = f; bs = s_; bt = t_; }
         }
     }

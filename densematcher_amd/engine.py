@@ -920,9 +920,11 @@ class MatchEngine:
             cache[name] = t
         return t
 
-    def precise_map(self, Phi1, Phi2, Cm, faces1, dense=False, scratch=False):
+    def precise_map(self, Phi1, Phi2, Cm, faces1, dense=False, scratch=False, return_info=False):
         """Barycentric projection of every vertex of mesh 2 onto the faces of mesh 1 in the spectral embedding (reference
-        get_precise_map, functional.py:221-251).  Returns (face_match (B,N2) int32, bary (B,N2,3) f64[, dense (B,N2,N1) f64])."""
+        get_precise_map, functional.py:221-251).  Returns (face_match (B,N2) int32, bary (B,N2,3) f64[, dense (B,N2,N1) f64]
+        [, info (B,) int32]).  return_info=True appends the route word of every pair: 1 if some point of the pair had more
+        candidate faces than the kernel lists and every face was re-tested for it, else 0 (same results either way)."""
         sfx, Phi1, Phi2 = self._reals(Phi1, Phi2)
         Cm = self._dev(Cm, torch.float64, "C")
         faces1 = self._dev(faces1, torch.int32, "faces1")
@@ -942,7 +944,8 @@ class MatchEngine:
         info = torch.empty((B,), dtype=torch.int32, device=self.device)
         self._chk(getattr(self.lib, "dm_precise_map" + sfx)(self.ctx, B, N1, N2, k1, k2, nf, _ptr(Phi1), ld1, _ptr(Phi2), ld2, _ptr(Cm), _ptr(faces1),
                                           _ptr(fm), _ptr(bary), _ptr(M), _ptr(info)))
-        return (fm, bary, M) if dense else (fm, bary)
+        out = (fm, bary, M) if dense else (fm, bary)
+        return out + (info,) if return_info else out
 
     def linear_sum_assignment(self, cost, maximize=False, defer=False):
         """Optimal assignment of every matrix of the batch `cost` (B,nr,nc) f64 -> col_of_row (B,nr) int32, -1 = unassigned

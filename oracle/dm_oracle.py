@@ -743,11 +743,15 @@ def _point_triangle(a, b, c, d, e, f, multi):
     return s_, t_, s_ * (a * s_ + b * t_ + 2.0 * d) + t_ * (b * s_ + c * t_ + 2.0 * e) + f
 
 
-def project_pc_to_triangles(vert_emb, faces, points_emb):
+def project_pc_to_triangles(vert_emb, faces, points_emb, details=None):
     """For every point the face of the embedded mesh it projects onto and the barycentric coordinates of the projection
     -- pyFM/spectral/projection_utils.py:16-115 (precompute_dmin = True): candidate faces are those whose nearest
     vertex is closer than the point's nearest vertex plus the face's longest edge (:356), the closest projection wins
-    (first face index on equal distances).  Returns (face_match (n2,), bary (n2,3))."""
+    (first face index on equal distances).  A candidate whose distance is NaN (a zero-area face: region 0 forms
+    0 * inf) is passed over -- the reference's argmin would name it and hand NaN weights on; the device skips it,
+    and so does this (precise map).  Returns (face_match (n2,), bary (n2,3)).
+    details: a list that receives one dict per point -- cand (face ids), dist (the distances the winner is chosen
+    on), abcdef (m,6) (the arguments of _point_triangle), multi -- for tests that need the runner-up or the region."""
     V = np.asarray(vert_emb, dtype=np.float64)
     P = np.asarray(points_emb, dtype=np.float64)
     faces = np.asarray(faces)
@@ -765,13 +769,20 @@ def project_pc_to_triangles(vert_emb, faces, points_emb):
         dmin = np.minimum(np.minimum(dv[faces[:, 0]], dv[faces[:, 1]]), dv[faces[:, 2]])           # :282-327
         cand = np.where(dmin - lmax < Deltamin[i])[0]                                              # :356
         multi = len(cand) > 1
-        best = None
+        best = (np.inf, 0, 0.0, 0.0)                      # (no sound candidate: face 0, weights (1, 0, 0), as the device)
+        rec = []
         for fi in cand:
             diff = e0[fi] - P[i]
-            s, t, sq = _point_triangle(fa[fi], fb[fi], fc[fi], ax1[fi] @ diff, ax2[fi] @ diff, diff @ diff, multi)
-            dist = np.sqrt(max(sq, 0.0))
-            if best is None or dist < best[0]:
+            args = (fa[fi], fb[fi], fc[fi], ax1[fi] @ diff, ax2[fi] @ diff, diff @ diff)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                s, t, sq = _point_triangle(*args, multi)
+                dist = np.sqrt(np.fmax(sq, 0.0)) if sq == sq else np.nan
+            rec.append(args + (dist,))
+            if dist < best[0]:
                 best = (dist, fi, s, t)
+        if details is not None:
+            rec = np.array(rec, dtype=np.float64).reshape(-1, 7)
+            details.append(dict(cand=cand, dist=rec[:, 6], abcdef=rec[:, :6], multi=multi))
         face_match[i] = best[1]
         bary[i] = (1.0 - best[2] - best[3], best[2], best[3])
     return face_match, bary
