@@ -71,6 +71,8 @@ SIGNATURES = {
     "dm_zoomout_sub": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p]),
     "dm_fps_euclid": (_i, [_p, _i, _i, _p, _p, _i, _p, _p]),
     "dm_fps_heat": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "dm_graph_geodesic": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
+    "dm_fps_graph": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

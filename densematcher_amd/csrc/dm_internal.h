@@ -60,6 +60,8 @@ struct dm_ctx {
     int opt_zoomout_sub_fused = 1;   // the Python layer's choice for subsampled ZoomOut: 1 = dm_zoomout_sub (one device loop), 0 = the host-chained
                                  // search + dm_p2p_to_fm_lstsq per iteration; the library only keeps the value
     int opt_fps_heat_route = 0;  // dm_fps_heat: 0 = the all-pairs rows when their work space fits, else one solve per sample; 1 / 2 force a route
+    int opt_graph_geod_device = 1;   // the Python layer's choice for shortest paths along mesh edges (the default extract_fps, get_geodesic(dijkstra=True)):
+                                 // 1 = dm_fps_graph / dm_graph_geodesic, 0 = SciPy's Dijkstra on the host; the same bits; the library only keeps the value
     int opt_energy_keep_gram = 0;  // 1: dm_fmap_energy_grad keeps P = A A^T, Q = B A^T of its FIRST call and reuses them while A, B
                                    // (pointers and sizes) stay the same: the caller promises not to change their contents (the L-BFGS
                                    // driver: the projected descriptors are fixed during a fit).  Setting the option again drops them.

@@ -68,6 +68,11 @@ def heat_geodesic_check(V, F, mass, b=0):
                          "the cotangent Laplacian's W and A (process(robust=False) on a fresh mesh)")
 
 
+class GraphTooWide(ValueError):
+    """a graph outside what dm_graph_geodesic / dm_fps_graph take (more than 16384 vertices, a degree above
+    MatchEngine.GRAPH_MAX_DEGREE): the mesh layer answers it with SciPy's Dijkstra on the host, the same bits"""
+
+
 class MatchEngine:
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
@@ -127,7 +132,7 @@ class MatchEngine:
 
     OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0, "energy_keep_gram": 0,
                        "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
-                       "zoomout_sub_fused": 1, "fps_heat_route": 0}
+                       "zoomout_sub_fused": 1, "fps_heat_route": 0, "graph_geod_device": 1}
 
     def set_option(self, name, value):
         """Choose between code paths of the library (include/densematch.h: dm_set_option).  Most settings return the same
@@ -136,7 +141,9 @@ class MatchEngine:
         tests/test_gpu_solver_conditioning.py); "fit_f32" runs the fused fit's element loop in fp32 (the reference's precision) and
         "fit_mfma" chooses the summation order of its products, so both change the fused fit's bits; "zoomout_sub_fused" chooses
         between the one-factor device loop of subsampled ZoomOut (1) and the host-chained least-squares steps (0): the maps agree
-        to 1e-9, not bit for bit."""
+        to 1e-9, not bit for bit; "graph_geod_device" chooses between the device kernels (1) and SciPy's Dijkstra on the host (0) for
+        shortest paths along mesh edges (the default extract_fps / extract_fps_many, get_geodesic(dijkstra=True)): the two settings
+        agree bit for bit."""
         self._chk(self.lib.dm_set_option(self.ctx, name.encode(), int(value)))
         self._options[name] = int(value)
 
@@ -802,6 +809,111 @@ class MatchEngine:
         info_h = info.cpu().numpy()
         for b in np.flatnonzero(info_h):
             raise ValueError(f"fps_heat: mesh {int(b)}: " + ("a start vertex outside the mesh" if info_h[b] & 1 else "a distance that is not finite"))
+        return out
+
+    # ------------------------------------------------------------- shortest paths along mesh edges (dm_graph_geodesic / dm_fps_graph)
+    GRAPH_MAX_DEGREE = 64
+    _GRAPH_INFO = ((1, "a source or start vertex outside the mesh"),
+                   (2, "an edge weight that is negative or NaN (shortest paths by relaxation need weights >= 0)"),
+                   (4, "a column outside the mesh's vertices"))
+
+    def _graph_ell(self, graphs, who):
+        """the ELL operands of dm_graph_geodesic / dm_fps_graph for a list of SciPy sparse matrices: G[i, j] stored = an edge i -> j
+        of that weight (explicit zeros included, as csgraph reads a sparse matrix).  Vertex-minor layout (B, nnz, N), vertex v's
+        entries = the edges INTO v, meshes padded to the largest, the width = the largest in-degree of the batch.  A degree above
+        GRAPH_MAX_DEGREE = 64 raises GraphTooWide (a ValueError): every vertex of every mesh walks the padded width in every sweep, so
+        one hub vertex would set the cost of the whole batch; mesh edge graphs stay far below (valence 6 on average)."""
+        import numpy as np
+        import scipy.sparse as sp
+        Bn = len(graphs)
+        if Bn == 0:
+            raise ValueError(f"{who}: no graphs")
+        ins, n_verts = [], []
+        for b, G in enumerate(graphs):
+            if not sp.issparse(G) or G.shape[0] != G.shape[1] or G.shape[0] < 1:
+                raise ValueError(f"{who}: mesh {b}: a square SciPy sparse matrix is expected")
+            Gi = sp.csc_matrix(G)                                                # column v = the edges into v (no entry is dropped or summed)
+            ins.append(Gi)
+            n_verts.append(Gi.shape[0])
+        N = max(n_verts)
+        if N > 16384:
+            raise GraphTooWide(f"{who}: meshes of up to 16384 vertices (got {N})")
+        nnz = max(1, max(int(np.diff(Gi.indptr).max()) for Gi in ins))
+        if nnz > self.GRAPH_MAX_DEGREE:
+            raise GraphTooWide(f"{who}: a vertex of degree {nnz}: the device route takes degrees up to {self.GRAPH_MAX_DEGREE}")
+        cols_h = np.full((Bn, nnz, N), -1, np.int32)
+        w_h = np.zeros((Bn, nnz, N), np.float64)
+        for b, Gi in enumerate(ins):
+            rl = np.diff(Gi.indptr)
+            pos = np.arange(Gi.nnz) - np.repeat(Gi.indptr[:-1], rl)
+            v = np.repeat(np.arange(Gi.shape[0]), rl)
+            cols_h[b, pos, v] = Gi.indices
+            w_h[b, pos, v] = Gi.data
+        nv_d = torch.as_tensor(np.asarray(n_verts, np.int32)).to(self.device)
+        return {"B": Bn, "N": N, "nnz": nnz, "n_verts": n_verts, "nv_d": nv_d,
+                "cols": torch.as_tensor(cols_h).to(self.device), "w": torch.as_tensor(w_h).to(self.device)}
+
+    def _graph_info(self, info, who):
+        import numpy as np
+        info_h = info.cpu().numpy()
+        for b in np.flatnonzero(info_h):
+            raise ValueError(f"{who}: mesh {int(b)}: " + "; ".join(msg for bit, msg in self._GRAPH_INFO if info_h[b] & bit))
+
+    def graph_geodesic(self, graphs, sources=None):
+        """Shortest-path distances on weighted graphs (dm_graph_geodesic): scipy.sparse.csgraph.dijkstra(G, indices=sources) BIT FOR
+        BIT, the reference's geodesic_distmat_dijkstra (geometry.py:524-556) when G is the edge graph of a mesh.
+        graphs: list of square SciPy sparse matrices, G[i, j] stored = an edge i -> j (store both directions of an undirected edge;
+        explicit zeros are edges), weights >= 0 (negative or NaN: ValueError); up to 16384 vertices, degrees up to GRAPH_MAX_DEGREE
+        (GraphTooWide, a ValueError, beyond either).
+        sources: None = all pairs; a 1-D list of vertex indices shared by every mesh; or one list per mesh (the same length, -1 = none).
+        Returns a device tensor D (B, ns, N) float64 with D[b, s] = the distances FROM sources[s] (row s of csgraph.dijkstra's
+        matrix; +inf where no path leads; columns past a mesh's vertex count and rows without a source are 0).  A row's bits do not
+        depend on the other sources or meshes of the call."""
+        import numpy as np
+        ell = self._graph_ell(graphs, "graph_geodesic")
+        Bn, N, nv = ell["B"], ell["N"], ell["n_verts"]
+        if sources is None:
+            src = np.full((Bn, N), -1, np.int32)
+            for b, n in enumerate(nv):
+                src[b, :n] = np.arange(n)
+        else:
+            src = np.asarray(sources)
+            src = np.broadcast_to(src, (Bn, src.shape[-1])) if src.ndim == 1 else src
+            if src.ndim != 2 or src.shape[0] != Bn or src.shape[1] == 0:
+                raise ValueError(f"graph_geodesic: sources must be (ns,) or ({Bn}, ns)")
+            for b, n in enumerate(nv):
+                if src[b].min() < -1 or src[b].max() >= n:
+                    raise ValueError(f"graph_geodesic: mesh {b}: source indices must lie in [0, {n})")
+            src = np.ascontiguousarray(src, np.int32)
+        ns = src.shape[1]
+        src_d = torch.as_tensor(src).to(self.device)
+        D = torch.empty((Bn, ns, N), dtype=torch.float64, device=self.device)
+        info = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_graph_geodesic(self.ctx, Bn, N, ell["nnz"], _ptr(ell["cols"]), _ptr(ell["w"]), _ptr(ell["nv_d"]), ns,
+                                             _ptr(src_d), _ptr(D), _ptr(info)))
+        self._graph_info(info, "graph_geodesic")
+        return D
+
+    def fps_graph(self, graphs, size, start):
+        """Farthest-point sampling on the shortest-path distances of graph_geodesic (dm_fps_graph): the loop of geometry.py:839-848 with
+        d(i) = csgraph.dijkstra(G, indices=i), the same indices (+inf is a maximum, the lowest index among equal maxima).
+        graphs as for graph_geodesic; start: one index or one per mesh.  Returns (B,size) int32 on the device.  The whole sampling
+        of the batch is ONE launch without host synchronisation."""
+        import numpy as np
+        ell = self._graph_ell(graphs, "fps_graph")
+        Bn = ell["B"]
+        if int(size) < 1:
+            raise ValueError("fps_graph: size must be positive")
+        st = np.broadcast_to(np.asarray(start, np.int64), (Bn,))
+        for b, n in enumerate(ell["n_verts"]):
+            if st[b] < 0 or st[b] >= n:
+                raise ValueError(f"fps_graph: mesh {b}: the start vertex must lie in [0, {n})")
+        st_d = torch.as_tensor(np.ascontiguousarray(st, np.int32)).to(self.device)
+        out = torch.empty((Bn, int(size)), dtype=torch.int32, device=self.device)
+        info = torch.zeros(Bn, dtype=torch.int32, device=self.device)
+        self._chk(self.lib.dm_fps_graph(self.ctx, Bn, ell["N"], ell["nnz"], _ptr(ell["cols"]), _ptr(ell["w"]), _ptr(ell["nv_d"]), int(size),
+                                        _ptr(st_d), _ptr(out), _ptr(info)))
+        self._graph_info(info, "fps_graph")
         return out
 
     def eigenbasis(self, W_list, mass, k, guard=None, degree=30, tol=1e-9, max_rounds=12, seed=0, ell=None):

@@ -50,16 +50,49 @@ def compute_normals(vertices, faces):
     return normals
 
 
-def geodesic_distmat_dijkstra(vertices, faces):
-    """all-pairs shortest paths along the mesh edges (geometry.py:524-556), on the host with SciPy as in the reference"""
-    from scipy.sparse import csgraph
+def graph_engine():
+    """the engine whose kernels compute the shortest paths along mesh edges (dm_graph_geodesic / dm_fps_graph), or None where SciPy's
+    Dijkstra runs on the host instead: the option "graph_geod_device" = 0, or a process without a GPU (the host-only tools and
+    tests).  The two routes return the same bits."""
+    import torch
+    if not torch.cuda.is_available():
+        return None
+    from ...engine import default_engine
+    eng = default_engine()
+    return eng if eng.get_option("graph_geod_device") else None
+
+
+def edge_graph(vertices, faces):
+    """the weighted edge graph of geometry.py:524-556: every unique undirected edge stored in both directions, Euclidean lengths"""
     vertices = np.asarray(vertices)
     N = vertices.shape[0]
     edges = edges_from_faces(faces)
     I, J = edges[:, 0], edges[:, 1]
     V = np.linalg.norm(vertices[J] - vertices[I], axis=1)
-    graph = sparse.coo_matrix((np.concatenate([V, V]), (np.concatenate([I, J]), np.concatenate([J, I]))), shape=(N, N)).tocsc()
-    return csgraph.dijkstra(graph)
+    return sparse.coo_matrix((np.concatenate([V, V]), (np.concatenate([I, J]), np.concatenate([J, I]))), shape=(N, N)).tocsc()
+
+
+def geodesic_distmat_dijkstra_many(meshes):
+    """geodesic_distmat_dijkstra for a list of (vertices, faces): ONE device call for the batch (meshes padded to the largest, each
+    matrix bit-identical to its own call); the host loop where the device route does not apply.  Returns a list of (n, n) arrays."""
+    from ...engine import GraphTooWide
+    graphs = [edge_graph(V, F) for V, F in meshes]
+    eng = graph_engine()
+    if eng is not None:
+        try:
+            D = eng.graph_geodesic(graphs).cpu().numpy()
+            return [np.ascontiguousarray(D[b, :g.shape[0], :g.shape[0]]) for b, g in enumerate(graphs)]
+        except GraphTooWide:                                                     # more than 16384 vertices or a hub vertex: the host route
+            pass
+    from scipy.sparse import csgraph
+    return [csgraph.dijkstra(g) for g in graphs]
+
+
+def geodesic_distmat_dijkstra(vertices, faces):
+    """all-pairs shortest paths along the mesh edges (geometry.py:524-556): row i = the distances from vertex i, the bits of the
+    reference's csgraph.dijkstra.  On the device (dm_graph_geodesic) for meshes of up to 16384 vertices; SciPy on the host otherwise
+    (see graph_engine)."""
+    return geodesic_distmat_dijkstra_many([(vertices, faces)])[0]
 
 
 def heat_geodmat_robust(vertices, faces, verbose=False):

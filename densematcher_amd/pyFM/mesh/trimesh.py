@@ -360,8 +360,9 @@ class TriMesh:
         geodesic=True, robust=False: the reference's own heat method (`geod_from(i, robust=False)`), on the device with the
         factors cached on the mesh (dm_fps_heat).
         geodesic=True, robust=True (the defaults): the reference measures with the heat method of the external potpourri3d wheel;
-        here the distance is the shortest path along mesh edges (Dijkstra on the edge graph, host) and a warning says so: the
-        samples spread the same way, they are not the same vertices.
+        here the distance is the shortest path along mesh edges (SciPy's Dijkstra distances on the edge graph, bit for bit; computed
+        by dm_fps_graph on the device up to 16384 vertices, on the host beyond) and a warning says so: the samples spread the same
+        way, they are not the same vertices.
         `rng`: numpy Generator for the start vertex (the reference draws from an unseeded one: its samples are not reproducible
         either); `start`: the first vertex itself."""
         n = self.n_vertices
@@ -382,14 +383,12 @@ class TriMesh:
             from ...engine import default_engine
             return default_engine().fps_heat(self._geodesic_factors(), size, start)[0].cpu().numpy().astype(np.int64)
         else:
+            self._warn_edge_paths()
+            G = self._fps_edge_graph()
+            got = TriMesh._fps_graph_device([G], size, [start])
+            if got is not None:
+                return got[0]
             import scipy.sparse.csgraph as csgraph
-            warnings.warn("extract_fps(geodesic=True): potpourri3d's heat-method geodesics are not available; using shortest paths "
-                          "along the mesh edges")
-            f = self.facelist
-            e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
-            w = np.linalg.norm(self.vertlist[e[:, 0]] - self.vertlist[e[:, 1]], axis=1)
-            G = sparse.coo_matrix((w, (e[:, 0], e[:, 1])), shape=(n, n)).tocsr()
-            G = G.maximum(G.T)
 
             def dist_from(i):
                 return csgraph.dijkstra(G, directed=False, indices=i)
@@ -400,6 +399,35 @@ class TriMesh:
             inds.append(newid)
             dists = np.minimum(dists, dist_from(newid))
         return np.asarray(inds)
+
+    @staticmethod
+    def _warn_edge_paths():
+        warnings.warn("extract_fps(geodesic=True): potpourri3d's heat-method geodesics are not available; using shortest paths "
+                      "along the mesh edges")
+
+    def _fps_edge_graph(self):
+        """the graph the default extract_fps measures on: the directed face edges summed into a CSR matrix (an edge that two faces
+        traverse in the same direction -- an inconsistently oriented mesh -- counts twice), then the larger of the two directions"""
+        n, f = self.n_vertices, self.facelist
+        e = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+        w = np.linalg.norm(self.vertlist[e[:, 0]] - self.vertlist[e[:, 1]], axis=1)
+        G = sparse.coo_matrix((w, (e[:, 0], e[:, 1])), shape=(n, n)).tocsr()
+        return G.maximum(G.T)
+
+    @staticmethod
+    def _fps_graph_device(graphs, size, starts):
+        """the samples of the default route on the device (dm_fps_graph: ONE launch for the batch), or None where the host loop runs:
+        "graph_geod_device" = 0, no GPU, more than 16384 vertices or a vertex of a degree above MatchEngine.GRAPH_MAX_DEGREE"""
+        from ...engine import GraphTooWide
+        from . import geometry
+        eng = geometry.graph_engine()
+        if eng is None:
+            return None
+        try:
+            out = eng.fps_graph(graphs, size, starts).cpu().numpy().astype(np.int64)
+        except GraphTooWide:
+            return None
+        return [out[b] for b in range(len(graphs))]
 
     @staticmethod
     def extract_fps_many(meshes, size, geodesic=True, robust=True, rng=None, starts=None):
@@ -414,6 +442,15 @@ class TriMesh:
         if len(starts) != len(meshes):
             raise ValueError("extract_fps_many: one start per mesh")
         nmax = max(mesh.n_vertices for mesh in meshes)
+        if geodesic and robust and nmax <= 16384:
+            for mesh, s in zip(meshes, starts):
+                if not 0 <= s < mesh.n_vertices:
+                    raise ValueError(f"extract_fps: the start vertex must lie in [0, {mesh.n_vertices})")
+            got = TriMesh._fps_graph_device([mesh._fps_edge_graph() for mesh in meshes], size, starts)
+            if got is not None:
+                for _ in meshes:                                                 # (one warning per mesh, as the single calls give)
+                    TriMesh._warn_edge_paths()
+                return got
         if (geodesic and robust) or nmax > 16384:
             return [mesh.extract_fps(size, geodesic=geodesic, robust=robust, start=s) for mesh, s in zip(meshes, starts)]
         from ...engine import default_engine
@@ -471,7 +508,7 @@ class TriMesh:
 
     def get_geodesic(self, dijkstra=False, robust=True, save=False, force_compute=False, sym=False, batch_size=500, verbose=False):
         """(n, n) geodesic distance matrix, column j = distances from vertex j (trimesh.py:612-692).  dijkstra=True: shortest paths
-        along the edges (host).  robust=False: the reference's heat method on the mesh's W and A, on the device; the factors stay
+        along the edges (the reference's csgraph.dijkstra bits, computed on the device up to 16384 vertices).  robust=False: the reference's heat method on the mesh's W and A, on the device; the factors stay
         on the mesh for geod_from (release_geodesic_factors frees them).  robust=True needs the potpourri3d wheel (ImportError).
         save: mesh files are not handled here (the reference's ValueError('No path specified')); force_compute: there is no file
         cache to bypass; batch_size: accepted, the result does not depend on it."""
@@ -504,8 +541,11 @@ class TriMesh:
         """mesh.get_geodesic(...) for several meshes: ONE factorisation and ONE solve for the batch (meshes padded to the largest;
         each mesh's matrix is bit-identical to its own get_geodesic).  The batch's factors are freed on return (they are not
         cached on the meshes).  Returns a list of (n_b, n_b) arrays."""
-        if dijkstra or robust:
-            return [mesh.get_geodesic(dijkstra=dijkstra, robust=robust, sym=sym, verbose=verbose) for mesh in meshes]
+        if dijkstra:
+            from . import geometry
+            return geometry.geodesic_distmat_dijkstra_many([(mesh.vertlist, mesh.facelist) for mesh in meshes])
+        if robust:
+            return [mesh.get_geodesic(robust=robust, sym=sym, verbose=verbose) for mesh in meshes]
         from ...engine import default_engine
         eng = default_engine()
         fac = eng.heat_geodesic_factor([mesh._geod_operands() for mesh in meshes], [mesh._heat_time() for mesh in meshes])

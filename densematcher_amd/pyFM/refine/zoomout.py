@@ -97,12 +97,21 @@ def zoomout_refine(FM_12, evects1, evects2, nit=10, step=1, A2=None, subsample=N
     return _run(FM_12, evects1, evects2, nit, step, A2, return_p2p)
 
 
+def _sample_pair(mesh1, mesh2, size):
+    """(mesh1.extract_fps(size), mesh2.extract_fps(size)) as ONE sampling call for the two meshes (TriMesh.extract_fps_many: the
+    starts are drawn mesh 1 first, then mesh 2)"""
+    from ..mesh.trimesh import TriMesh
+    if isinstance(mesh1, TriMesh) and isinstance(mesh2, TriMesh):
+        return tuple(TriMesh.extract_fps_many([mesh1, mesh2], size))
+    return (mesh1.extract_fps(size), mesh2.extract_fps(size))
+
+
 def mesh_zoomout_refine(FM_12, mesh1, mesh2, nit=10, step=1, subsample=None, return_p2p=False, n_jobs=1, verbose=False):
     """reference zoomout.py:118-161"""
     if np.issubdtype(type(subsample), np.integer):                              # zoomout.py:151-155
         if verbose:
             print(f'Computing farthest point sampling of size {subsample}')
-        subsample = (mesh1.extract_fps(subsample), mesh2.extract_fps(subsample))
+        subsample = _sample_pair(mesh1, mesh2, subsample)
     return zoomout_refine(FM_12, mesh1.eigenvectors, mesh2.eigenvectors, nit, step=step, A2=mesh2.A, subsample=subsample,
                           return_p2p=return_p2p, n_jobs=n_jobs, verbose=verbose)
 
@@ -116,7 +125,7 @@ def mesh_zoomout_refine_p2p(p2p_21, mesh1, mesh2, k_init, nit=10, step=1, subsam
             raise ValueError("P2P can't be defined on undefined subsample")
         if verbose:
             print(f'Computing farthest point sampling of size {subsample}')
-        subsample = (mesh1.extract_fps(subsample), mesh2.extract_fps(subsample))
+        subsample = _sample_pair(mesh1, mesh2, subsample)
     FM_12_init = spectral.mesh_p2p_to_FM(p2p_21, mesh1, mesh2, dims=k_init, subsample=subsample if p2p_on_sub else None)
     return zoomout_refine(FM_12_init, mesh1.eigenvectors, mesh2.eigenvectors, nit, step=step, A2=mesh2.A, subsample=subsample,
                           return_p2p=return_p2p, n_jobs=n_jobs, verbose=verbose)

@@ -88,6 +88,9 @@ size_t dm_workspace_bytes(const dm_ctx* ctx);
  *                           iteration.  The library only keeps the value.  The two settings agree to 1e-9, not bit for bit.
  *   "fps_heat_route" 0 | 1 | 2   dm_fps_heat: the all-pairs rows when their work space fits, else one solve per sample | always the
  *                           all-pairs rows | always one solve per sample.  Same indices.
+ *   "graph_geod_device" 1 | 0   shortest paths along the mesh edges in the Python layer (the default TriMesh.extract_fps / extract_fps_many,
+ *                           get_geodesic(dijkstra=True), geometry.geodesic_distmat_dijkstra): dm_fps_graph / dm_graph_geodesic | SciPy's
+ *                           Dijkstra on the host.  The library only keeps the value.  The two settings agree bit for bit.
  *   "p2pfm_direct"  1 | 0   dm_p2p_to_fm (and the p2p_to_FM steps of dm_zoomout / dm_icp): register-resident tiles, operands straight
  *                           from global memory, fixed-order in-workgroup reduction | LDS-staged 64 x 64 tiles + split-K partials + reduce
  *   "simnn1_wt"     4 | 2   tile shape of the fused ZoomOut search: 8 waves, 256 x 256 | 4 waves, 128 x 256 (two workgroups per CU)
@@ -519,6 +522,32 @@ int dm_zoomout_sub_f64(dm_ctx* ctx, int B, int N1, int N2, int n1s, int n2s, con
 int dm_fps_euclid(dm_ctx* ctx, int B, int N, const double* verts, const int32_t* n_verts /*nullable*/, int size,
                   const int32_t* start, int32_t* out);
 int dm_fps_heat(dm_ctx* ctx, int B, int N, int nt, const void* factors, int size, const int32_t* start, int32_t* out, int32_t* info);
+
+/* ---- shortest paths along the edges of a mesh -------------------------------------------
+ * Replaces scipy.sparse.csgraph.dijkstra on the edge graph of a mesh: all pairs in pyFM/mesh/geometry.py:524-556
+ * (geodesic_distmat_dijkstra, behind TriMesh.get_geodesic(dijkstra=True), pyFM/mesh/trimesh.py:612-692, the matrix pyFM.eval.accuracy
+ * consumes), and one run per sample in the default TriMesh.extract_fps of this package.  The distances are Dijkstra's BIT FOR BIT:
+ * d[v] = the minimum over the paths s -> v of the left-folded float64 sum of the weights, reached by relaxing every edge until a
+ * whole sweep changes nothing -- for weights >= 0 that fixed point is unique, whatever the order of the relaxations (DESIGN.md
+ * section 4), so a row's bits depend neither on the other sources or meshes of a call nor on how the work is spread over threads.
+ * The graph of B meshes padded to N vertices (n_verts, nullable: the real count of each), ELL in VERTEX-MINOR layout:
+ * cols (B,nnz,N) int32, w (B,nnz,N) fp64; entry (b,e,v) is an edge INTO vertex v from vertex cols[b][e][v] of weight w[b][e][v]
+ * (an undirected graph stores every edge at both ends; a stored weight 0 is an edge), col = -1 pads.  N <= 16384 (8 N bytes of LDS
+ * hold the distances of one source).
+ *   dm_graph_geodesic  D (B,ns,N) fp64: row s of mesh b = the distances FROM vertex sources[b][s] (row i of csgraph.dijkstra's matrix);
+ *                      +inf for a vertex no path reaches; sources (B,ns) int32 device, -1 = no source (a row of zeros); columns past
+ *                      n_verts are 0.  One workgroup per source.
+ *   dm_fps_graph       farthest-point sampling (see above) with d(i) = row i of dm_graph_geodesic: out (B,size) int32, out[b][0] =
+ *                      start[b]; +inf counts as a maximum (the lowest-index vertex of an unreached component is taken next).  One
+ *                      workgroup per mesh runs the whole loop in ONE launch; the running minimum stays in LDS and every sample
+ *                      relaxes from it (min(m, d_new) exactly), which only touches the new sample's Voronoi region.
+ * info (B, zeroed by the caller), a sum of: 1 a source outside [-1, n_verts) / a start outside [0, n_verts) (a row of zeros / clamped);
+ * 2 a weight that is negative or NaN (the argument needs w >= 0; such an edge is skipped); 4 a column outside [-1, n_verts) (skipped).
+ * The results of a flagged mesh are not meaningful. */
+int dm_graph_geodesic(dm_ctx* ctx, int B, int N, int nnz, const int32_t* cols, const double* w, const int32_t* n_verts /*nullable*/,
+                      int ns, const int32_t* sources, double* D, int32_t* info);
+int dm_fps_graph(dm_ctx* ctx, int B, int N, int nnz, const int32_t* cols, const double* w, const int32_t* n_verts /*nullable*/,
+                 int size, const int32_t* start, int32_t* out, int32_t* info);
 
 /* ---- spectral ICP -------------------------------------------------------------
  * nit times: p21 = knn21(C); Chat = argmin |Phi2[:, :k2] X - Phi1[p21, :k1]|_F (no mass);
