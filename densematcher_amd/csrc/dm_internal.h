@@ -345,6 +345,12 @@ __device__ __forceinline__ void dm_c00_body(const dm_c00_args<TR>& z, int b, int
 }
 #endif
 
+// linear assignment of B dense nr x nc matrices (dm_assign.hip), for callers that gather their matrices themselves (dm_lsa_gather.hip):
+// the caller reserves lsa_ws_bytes(B, nr, nc) of the arena and zeroes info (B); the argument lists are those of lsa_run's definition
+size_t lsa_ws_bytes(int B, int nr, int nc);
+int lsa_run(dm_ctx* ctx, int B, int nr, int nc, const double* dense, int n_lr, int KP, const double* E2p, const double* P1p,
+            const double* a1p, int maximize, int32_t* col_of_row, int32_t* info);
+
 // fp16 split-operand MFMA projection (dm_project.hip); F must be fp16
 size_t dm_project_f16split_ws(int B, int N, int D, int k, int ld, int real_bytes);
 // cz (nullable): the maxima pass of this projection also computes the pinned entries c00 of the pairs (one more workgroup each)

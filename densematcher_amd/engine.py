@@ -1081,6 +1081,138 @@ class MatchEngine:
             return out
         return finish if defer else finish()
 
+    # ------------------------------------------------------------- ragged assignments gathered from one matrix (dm_lsa_gather)
+    def _lsa_gather_D(self, D, who):
+        """D as the (B, N, ld) float64 device operand of dm_lsa_gather: a device tensor is used where it is when its strides fit the
+        ABI (unit stride along a row, one row stride ld >= N, meshes N ld apart); anything else is copied.  Returns (tensor, B, N, ld)."""
+        if not isinstance(D, torch.Tensor):
+            import warnings
+            with warnings.catch_warnings():                  # (a read-only array is only read)
+                warnings.simplefilter("ignore", UserWarning)
+                D = torch.as_tensor(D)
+        if D.dim() == 2:
+            D = D[None]
+        if D.dim() != 3 or D.shape[1] != D.shape[2] or D.shape[1] < 1:
+            raise ValueError(f"{who}: D must be (N, N) or (B, N, N)")
+        B, N = int(D.shape[0]), int(D.shape[1])
+        fits = (D.device == self.device and D.dtype == torch.float64 and D.stride(2) == 1 and D.stride(1) >= N and
+                D.stride(1) < 2 ** 31 and (B == 1 or D.stride(0) == N * D.stride(1)))
+        if not fits:
+            D = self._dev(D, torch.float64, "D")
+        else:
+            self._dev(D[:0], torch.float64, "D")              # (the stream check)
+        return D, B, N, int(D.stride(1))
+
+    def _lsa_gather_run(self, D, idx, table, maximize, return_assignment, n_out):
+        """dm_lsa_gather on a prepared index array (n_idx,) and problem table (P, 6), both int32 NumPy; the means (P,) float64 and,
+        on request, the packed col_of_row (n_out,) int32, as NumPy arrays.  Raises SciPy's errors."""
+        import numpy as np
+        Dd, B, N, ld = D
+        P = int(table.shape[0])
+        if P == 0:
+            return np.zeros(0, np.float64), (np.zeros(0, np.int32) if return_assignment else None)
+        idx_d = torch.as_tensor(np.ascontiguousarray(idx, np.int32)).to(self.device)
+        table = np.ascontiguousarray(table, np.int32)
+        mean = torch.empty((P,), dtype=torch.float64, device=self.device)
+        info = torch.empty((P,), dtype=torch.int32, device=self.device)
+        out = torch.empty((max(1, n_out),), dtype=torch.int32, device=self.device) if return_assignment else None
+        self._chk(self.lib.dm_lsa_gather(self.ctx, B, N, ld, _ptr(Dd), int(idx_d.numel()), _ptr(idx_d), P,
+                                         C.c_void_p(table.ctypes.data), 1 if maximize else 0, _ptr(out), _ptr(mean), _ptr(info)))
+        worst = int(info.max())
+        if worst == 2:
+            raise ValueError("matrix contains invalid numeric entries")      # SciPy's messages
+        if worst == 1:
+            raise ValueError("cost matrix is infeasible")
+        return mean.cpu().numpy(), (out.cpu().numpy() if return_assignment else None)
+
+    @staticmethod
+    def _index_list(lst, n, who):
+        import numpy as np
+        a = np.asarray(lst)
+        if a.ndim != 1:
+            raise ValueError(f"{who}: an index list must be one-dimensional")
+        if a.size and not (np.issubdtype(a.dtype, np.integer) or np.issubdtype(a.dtype, np.bool_)):
+            raise ValueError(f"{who}: an index list must hold integers")
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= n):
+            raise ValueError(f"{who}: vertex indices must lie in [0, {n})")
+        return a.astype(np.int32)
+
+    def lsa_gather(self, D, row_lists, col_lists, mesh=None, maximize=False, return_assignment=False, n_verts=None):
+        """Many assignments on sub-blocks of one matrix in ONE device call (dm_lsa_gather): problem p is
+        scipy.optimize.linear_sum_assignment(D[mesh[p]][np.ix_(row_lists[p], col_lists[p])], maximize) -- the same assignment, ties
+        included -- and the mean of its matched entries (the reference's get_distance_between_groups, densematcher/utils.py:115-127).
+        D: (N, N) or (B, N, N), NumPy or torch; a float64 device tensor is read in place (a padded batch as heat_geodesic /
+        graph_geodesic return it, or a view of one with a row stride).  row_lists / col_lists: P sequences of vertex indices
+        (repeats and overlaps allowed, none empty); mesh: the mesh of every problem (default 0); n_verts (B,): the vertex counts of a
+        padded batch, for the index check (default N).
+        Returns the means (P,) float64 (NumPy); with return_assignment=True also the list of col_of_row arrays (int32, -1 for an
+        unassigned row when a problem has more rows than columns).  ValueError with SciPy's texts for an infeasible problem and for
+        NaN / the rejected infinity; ValueError for an index outside its mesh and for an empty list."""
+        import numpy as np
+        Dt = self._lsa_gather_D(D, "lsa_gather")
+        B, N = Dt[1], Dt[2]
+        P = len(row_lists)
+        if len(col_lists) != P:
+            raise ValueError("lsa_gather: as many column lists as row lists")
+        mesh = np.zeros(P, np.int64) if mesh is None else np.broadcast_to(np.asarray(mesh, np.int64), (P,))
+        if P and (mesh.min() < 0 or mesh.max() >= B):
+            raise ValueError(f"lsa_gather: mesh indices must lie in [0, {B})")
+        nv = np.full(B, N, np.int64) if n_verts is None else np.broadcast_to(np.asarray(n_verts, np.int64), (B,))
+        if nv.min() < 1 or nv.max() > N:
+            raise ValueError("lsa_gather: n_verts must lie in [1, N]")
+        parts, table, off, ooff = [], np.zeros((P, 6), np.int32), 0, 0
+        for p in range(P):
+            r = self._index_list(row_lists[p], int(nv[mesh[p]]), "lsa_gather")
+            c = self._index_list(col_lists[p], int(nv[mesh[p]]), "lsa_gather")
+            if r.size == 0 or c.size == 0:
+                raise ValueError(f"lsa_gather: problem {p}: an empty index list")
+            table[p] = (mesh[p], off, r.size, off + r.size, c.size, ooff)
+            parts += [r, c]
+            off += r.size + c.size
+            ooff += r.size
+        idx = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        means, packed = self._lsa_gather_run(Dt, idx, table, maximize, return_assignment, ooff)
+        if not return_assignment:
+            return means
+        return means, [packed[table[p, 5]:table[p, 5] + table[p, 2]] for p in range(P)]
+
+    def groups_dmtx(self, D, groups, n_verts=None):
+        """The semantic distance matrices between vertex groups (the reference's get_groups_dmtx, densematcher/utils.py:129-143) of
+        a batch of meshes in ONE lsa_gather call: out[i, j] = out[j, i] (i < j) = the mean matched distance of the assignment on
+        D[np.ix_(groups[i], groups[j])], 0 on the diagonal and for a pair with an empty group.
+        D (N, N) with one list of groups -> one (G, G) float64 NumPy array; D (B, N, N) (meshes padded to the largest, n_verts (B,)
+        their vertex counts) with one list of groups per mesh (any numbers of groups) -> a list of B arrays."""
+        import numpy as np
+        single = (D.dim() if isinstance(D, torch.Tensor) else np.ndim(D)) == 2
+        Dt = self._lsa_gather_D(D, "groups_dmtx")
+        B, N = Dt[1], Dt[2]
+        per_mesh = [groups] if single else list(groups)
+        if len(per_mesh) != B:
+            raise ValueError(f"groups_dmtx: {len(per_mesh)} lists of groups for {B} meshes")
+        nv = np.full(B, N, np.int64) if n_verts is None else np.broadcast_to(np.asarray(n_verts, np.int64), (B,))
+        if nv.min() < 1 or nv.max() > N:
+            raise ValueError("groups_dmtx: n_verts must lie in [1, N]")
+        parts, off, rows, where = [], 0, [], []
+        for b, gs in enumerate(per_mesh):
+            lists = [self._index_list(g, int(nv[b]), f"groups_dmtx: mesh {b}") for g in gs]
+            offs = []
+            for g in lists:                                  # every group once in the index array, whatever the number of its pairs
+                offs.append(off)
+                parts.append(g)
+                off += g.size
+            for i in range(len(lists)):
+                for j in range(i + 1, len(lists)):
+                    if lists[i].size and lists[j].size:
+                        rows.append((b, offs[i], lists[i].size, offs[j], lists[j].size, 0))
+                        where.append((b, i, j))
+        table = np.asarray(rows, np.int32).reshape(-1, 6)
+        idx = np.concatenate(parts) if parts else np.zeros(0, np.int32)
+        means, _ = self._lsa_gather_run(Dt, idx, table, False, False, 0)
+        out = [np.zeros((len(gs), len(gs)), np.float64) for gs in per_mesh]
+        for (b, i, j), m in zip(where, means):
+            out[b][i, j] = out[b][j, i] = m
+        return out[0] if single else out
+
     def lsa_indicator_ok(self, N1, N2, k1, k2):
         return bool(self.lib.dm_lsa_indicator_ok(self.ctx, int(N1), int(N2), int(k1), int(k2)))
 

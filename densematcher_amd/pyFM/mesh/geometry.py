@@ -75,17 +75,26 @@ def edge_graph(vertices, faces):
 def geodesic_distmat_dijkstra_many(meshes):
     """geodesic_distmat_dijkstra for a list of (vertices, faces): ONE device call for the batch (meshes padded to the largest, each
     matrix bit-identical to its own call); the host loop where the device route does not apply.  Returns a list of (n, n) arrays."""
-    from ...engine import GraphTooWide
     graphs = [edge_graph(V, F) for V, F in meshes]
-    eng = graph_engine()
-    if eng is not None:
-        try:
-            D = eng.graph_geodesic(graphs).cpu().numpy()
-            return [np.ascontiguousarray(D[b, :g.shape[0], :g.shape[0]]) for b, g in enumerate(graphs)]
-        except GraphTooWide:                                                     # more than 16384 vertices or a hub vertex: the host route
-            pass
+    D = _dijkstra_many_device(graphs)
+    if D is not None:
+        D = D.cpu().numpy()
+        return [np.ascontiguousarray(D[b, :g.shape[0], :g.shape[0]]) for b, g in enumerate(graphs)]
     from scipy.sparse import csgraph
     return [csgraph.dijkstra(g) for g in graphs]
+
+
+def _dijkstra_many_device(graphs):
+    """the padded (B, N, N) device tensor of the all-pairs shortest paths of the edge graphs, or None where the device route does not
+    apply (graph_engine; more than 16384 vertices or a hub vertex)"""
+    from ...engine import GraphTooWide
+    eng = graph_engine()
+    if eng is None:
+        return None
+    try:
+        return eng.graph_geodesic(graphs)
+    except GraphTooWide:
+        return None
 
 
 def geodesic_distmat_dijkstra(vertices, faces):

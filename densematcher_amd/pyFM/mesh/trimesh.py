@@ -546,11 +546,48 @@ class TriMesh:
             return geometry.geodesic_distmat_dijkstra_many([(mesh.vertlist, mesh.facelist) for mesh in meshes])
         if robust:
             return [mesh.get_geodesic(robust=robust, sym=sym, verbose=verbose) for mesh in meshes]
+        D = TriMesh._heat_geodesic_many_device(meshes, sym).cpu().numpy()
+        return [np.ascontiguousarray(D[b, :mesh.n_vertices, :mesh.n_vertices]) for b, mesh in enumerate(meshes)]
+
+    @staticmethod
+    def _heat_geodesic_many_device(meshes, sym):
+        """the heat-method matrices of get_geodesic_many(robust=False) as the padded (B, N, N) device tensor they are computed in"""
         from ...engine import default_engine
         eng = default_engine()
         fac = eng.heat_geodesic_factor([mesh._geod_operands() for mesh in meshes], [mesh._heat_time() for mesh in meshes])
-        D = eng.heat_geodesic(fac, sym=sym).cpu().numpy()
-        return [np.ascontiguousarray(D[b, :mesh.n_vertices, :mesh.n_vertices]) for b, mesh in enumerate(meshes)]
+        return eng.heat_geodesic(fac, sym=sym)
+
+    def get_groups_dmtx(self, groups, dijkstra=False, robust=True, sym=False):
+        """(G, G) semantic distance matrix between the vertex groups `groups` on this mesh's geodesic distances: the reference's
+        get_groups_dmtx(mesh.get_geodesic(dijkstra, robust, sym=sym), groups) (densematcher/utils.py:129-143).  See
+        get_groups_dmtx_many."""
+        return TriMesh.get_groups_dmtx_many([self], [groups], dijkstra=dijkstra, robust=robust, sym=sym)[0]
+
+    @staticmethod
+    def get_groups_dmtx_many(meshes, groups_list, dijkstra=False, robust=True, sym=False):
+        """densematcher_amd.utils.get_groups_dmtx on the matrices of get_geodesic_many(meshes, dijkstra, robust, sym), one list of
+        groups per mesh.  With dijkstra=True or robust=False the distances are computed on the device and consumed there by ONE
+        assignment call for the batch: no N x N matrix crosses to the host.  robust=True needs the potpourri3d wheel (ImportError),
+        whose matrices are host arrays; they and the matrices of meshes outside the device's shortest-path route (more than 16384
+        vertices) go through densematcher_amd.utils.get_groups_dmtx_many.  Returns a list of (G_b, G_b) arrays."""
+        from ... import utils
+        meshes, groups_list = list(meshes), [list(g) for g in groups_list]
+        if len(meshes) != len(groups_list):
+            raise ValueError(f"get_groups_dmtx_many: {len(groups_list)} lists of groups for {len(meshes)} meshes")
+        if len(meshes) == 0:
+            return []
+        D = None
+        if dijkstra:
+            from . import geometry
+            D = geometry._dijkstra_many_device([geometry.edge_graph(mesh.vertlist, mesh.facelist) for mesh in meshes])
+        elif not robust:
+            D = TriMesh._heat_geodesic_many_device(meshes, sym)
+        if D is None:
+            return utils.get_groups_dmtx_many(TriMesh.get_geodesic_many(meshes, dijkstra=dijkstra, robust=robust, sym=sym), groups_list)
+        from ...engine import default_engine
+        for g in groups_list:
+            utils._warn_empty(g)
+        return default_engine().groups_dmtx(D, groups_list, n_verts=[mesh.n_vertices for mesh in meshes])
 
     # ------------------------------------------------------------- spectral helpers
     def project(self, func, k=None):

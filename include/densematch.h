@@ -465,6 +465,26 @@ int dm_precise_map_f64(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int n
 int dm_linear_sum_assignment(dm_ctx* ctx, int B, int nr, int nc, const double* cost, int maximize,
                              int32_t* col_of_row /* B*nr */, int32_t* info /* B */);
 
+/* ---- many ragged assignments gathered from one matrix -----------------------------
+ * Replaces the loop of densematcher/utils.py:115-143 (get_distance_between_groups / get_groups_dmtx: the semantic distance matrix
+ * between vertex groups): for every problem p,  scipy.optimize.linear_sum_assignment(S_p)  with  S_p[r][c] = D[b][rows[r]][cols[c]]
+ * and the mean of the matched entries.  D (B,N,ld) fp64 device, row stride ld >= N (the padded batches of the geodesic calls), is
+ * read where it is.  idx (n_idx) int32 device: every index list of the call, concatenated.  problems (P,6) int32 in HOST memory
+ * (the library orders the problems by work, largest first, and uploads the table): mesh b, offset and length nr of the row list in
+ * idx, offset and length nc of the column list, offset of the problem's nr outputs in col_of_row.  Lists may repeat indices and
+ * overlap.  Indices must lie in [0, N) (the caller checks, as for dm_precise_map; the kernels index D with them).
+ * Outputs (device): col_of_row (nullable) packed by the output offsets, -1 for an unassigned row (nr > nc); mean (P) = the matched
+ * entries S_p[r][col_of_row[r]] summed over the assigned rows r in ascending order, divided by min(nr, nc); info (P) with the codes
+ * of dm_linear_sum_assignment: 0 ok, 1 infeasible, 2 NaN or an infinity of the rejected sign (mean = NaN, col_of_row = -1 there).
+ * Same algorithm, floating-point steps and tie rules as SciPy's (the transposed problem is solved when nr > nc, as SciPy does): the
+ * assignment equals SciPy's, ties included.  One wavefront per problem for up to 1024 entries on the longer side, the
+ * workgroup-per-matrix search of dm_linear_sum_assignment on a gathered copy above; a problem's results do not depend on what else
+ * shares the call.  P = 0 is legal (nothing is launched); nr = 0 or nc = 0 is DM_EINVAL.  The call synchronises the stream once
+ * (the table's upload). */
+int dm_lsa_gather(dm_ctx* ctx, int B, int N, int ld, const double* D, int n_idx, const int32_t* idx, int P,
+                  const int32_t* problems /* host, P*6 */, int maximize, int32_t* col_of_row /*nullable*/, double* mean /* P */,
+                  int32_t* info /* P */);
+
 /* ---- vertex map -> functional map, least squares -------------------------------
  * C[b] = argmin_X |Phi2[b][:, :k2] X - Phi1[b][p21[b], :k1]|_F   (k2 x k1) fp64, no mass matrix.
  * Replaces pyFM/spectral/convert.py:51 (p2p_to_FM with A2 = None: scipy.linalg.lstsq), the form ICP and ZoomOut on
