@@ -74,11 +74,12 @@ SIGNATURES = {
     "dm_fps_heat": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dm_graph_geodesic": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "dm_fps_graph": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
+    "dm_spectral_signatures": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists
 for _n in ("dm_project", "dm_fmap_fit", "dm_fmap_c00", "dm_fm_to_p2p", "dm_mapped_indicator", "dm_p2p_to_fm", "dm_precise_map", "dm_p2p_to_fm_lstsq", "dm_icp", "dm_lsa_indicator",
-           "dm_zoomout", "dm_zoomout_sub"):
+           "dm_zoomout", "dm_zoomout_sub", "dm_spectral_signatures"):
     SIGNATURES[_n + "_f64"] = SIGNATURES[_n]
 
 _libs = {}

@@ -1358,6 +1358,52 @@ class MatchEngine:
                                                _ptr(Cm), _ptr(M)))
         return M
 
+    # ------------------------------------------------------------------ spectral descriptors
+    def signatures(self, Phi, lam, kind, num, landmarks=None, plain=True, k=None, n_verts=None, out_dtype=torch.float64):
+        """Heat / wave kernel signatures (pyFM/signatures.py: mesh_HKS / mesh_WKS, reference functional.py:308-334) of a batch of
+        meshes: Phi (B,N,ld) f32|f64 eigenvectors, lam (B,>=k) eigenvalues, kind "HKS" | "WKS", num times / energies, landmarks
+        None | (B,P) vertex indices, plain: the vertex's own block leads, k: eigenpairs used (default: all of lam), n_verts (B):
+        vertex counts of meshes padded to N.  Returns (B, N, (plain + P) num) on the device, float64 or float32 (rounded once
+        from the float64 value), columns [plain | landmark 0 | landmark 1 | ...]; rows past n_verts are 0."""
+        import numpy as np
+        from .pyFM.signatures import signature_tables
+        if out_dtype not in (torch.float64, torch.float32):
+            raise ValueError("signatures: out_dtype must be torch.float64 or torch.float32")
+        sfx, Phi = self._reals(Phi)
+        if Phi.dim() != 3:
+            raise ValueError("signatures: Phi must be (B,N,ld)")
+        B, N, ld = Phi.shape
+        lam = np.asarray(lam.detach().cpu() if isinstance(lam, torch.Tensor) else lam, dtype=np.float64)
+        if lam.ndim != 2 or lam.shape[0] != B:
+            raise ValueError("signatures: lam must be (B,k)")
+        K = lam.shape[1] if k is None else min(int(k), lam.shape[1])
+        if K < 2 or K > ld:
+            raise ValueError(f"signatures: {K} eigenpairs with {ld} eigenvector columns (at least 2 are needed)")
+        num = int(num)
+        if num < 1:
+            raise ValueError("signatures: at least one time / energy (num >= 1)")
+        plain = 1 if plain else 0
+        lm = np.zeros((B, 0), np.int32) if landmarks is None else np.ascontiguousarray(np.asarray(landmarks).reshape(B, -1), dtype=np.int32)
+        P = lm.shape[1]
+        if plain + P < 1:
+            raise ValueError("signatures: nothing to compute (plain=False and no landmark)")
+        nv = None if n_verts is None else np.ascontiguousarray(np.asarray(n_verts).reshape(B), dtype=np.int32)
+        if nv is not None and (nv.min() < 0 or nv.max() > N):
+            raise ValueError("signatures: n_verts must lie in [0, N]")
+        if P and (lm.min() < 0 or (lm >= (N if nv is None else nv[:, None])).any()):
+            raise ValueError("signatures: landmarks must lie in [0, n_verts)")
+        tabs = [(signature_tables(lam[b, :K], kind, num, False), signature_tables(lam[b, :K], kind, num, True)) for b in range(B)]
+        t = self._dev(np.stack([tb[0][0] for tb in tabs]), torch.float64, "t")
+        mu = self._dev(np.stack([tb[0][1] for tb in tabs]), torch.float64, "mu")
+        denom = self._dev(np.array([tb[0][2] for tb in tabs], dtype=np.float64), torch.float64, "denom")
+        k0 = np.ascontiguousarray([[tb[0][3], tb[1][3]] for tb in tabs], dtype=np.int32)
+        out = torch.empty((B, N, (plain + P) * num), dtype=out_dtype, device=self.device)
+        ip = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
+        self._chk(getattr(self.lib, "dm_spectral_signatures" + sfx)(
+            self.ctx, B, N, ip(nv), K, _ptr(Phi), ld, {"HKS": 0, "WKS": 1}[kind], num, _ptr(t), _ptr(mu), _ptr(denom), ip(k0), P, ip(lm),
+            plain, 1 if out_dtype == torch.float32 else 0, _ptr(out)))
+        return out
+
     # ------------------------------------------------------------------ the hot path, one batch
     def match(self, batch, k=None, w_descr=1e4, w_lap=1e3, knn=True, ind=True, check=False):
         """project -> pinned column -> solve -> vertex maps for a batch of pairs (BASELINE config 2).

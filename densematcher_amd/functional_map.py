@@ -120,8 +120,10 @@ class _robust_backend_for_call:
 
 
 def compute_surface_map(mesh1_t, mesh2_t, c1, c2, n_ev=50, compute_extra=False, optimizer="fmin_l_bfgs_b", descr_type="neural",
-                        maxiter=100000, optimize_p2p=False, fit_params=None, robust_backend=None):
+                        maxiter=100000, optimize_p2p=False, fit_params=None, robust_backend=None, signature_route="host"):
     '''
+    signature_route (not in the reference): "host" | "device", where descr_type "HKS" / "WKS" is evaluated (FunctionalMapping.preprocess);
+        "device" is the route compute_surface_map_batch takes.
     robust_backend (not in the reference): the Laplacians are built with robust=True like the reference's (functional.py:294-295), which
         calls the `robust_laplacian` wheel.  Where that wheel is not installed the call raises ImportError -- unless
         robust_backend="restated" (or laplacian.set_robust_backend / DENSEMATCHER_AMD_ROBUST_LAPLACIAN) opts into this package's own
@@ -140,7 +142,7 @@ def compute_surface_map(mesh1_t, mesh2_t, c1, c2, n_ev=50, compute_extra=False, 
                           'subsample_step': 1}
     else:                                     # spectral signatures instead of network features (functional_map.py:19-35)
         process_params = {'n_ev': (n_ev, n_ev), 'n_descr': 16 if descr_type == "HKS" else 2048, 'landmarks': None,
-                          'descr_type': descr_type, 'subsample_step': 1}
+                          'descr_type': descr_type, 'subsample_step': 1, 'signature_route': signature_route}
     model = FunctionalMapping(mesh1, mesh2, partial=False, optimizer=optimizer)
     with _robust_backend_for_call(robust_backend):
         model.preprocess(**process_params, verbose=False)
@@ -212,12 +214,16 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
     import torch
     from .engine import default_engine
     from .pyFM.spectral.convert import MappedIndicator, _real_dtype
+    from .pyFM.signatures import LazySignature
     eng = default_engine()
     groups = {}
     for i in idx:
         model = models[i]
-        key = (model.mesh1.n_vertices, model.mesh2.n_vertices, model.mesh1.facelist.shape[0], model.descr1.shape[1],
-               str(model.descr1.dtype), str(model.descr2.dtype))
+        if isinstance(model.descr1, LazySignature):   # spectral signatures: computed on the device after the eigenbases, nothing to stage
+            key = (model.mesh1.n_vertices, model.mesh2.n_vertices, model.mesh1.facelist.shape[0], model.descr1.kind, model.descr1.num)
+        else:
+            key = (model.mesh1.n_vertices, model.mesh2.n_vertices, model.mesh1.facelist.shape[0], model.descr1.shape[1],
+                   str(model.descr1.dtype), str(model.descr2.dtype))
         groups.setdefault(key, []).append(i)
     # The descriptors do not wait for the eigenbases: a helper thread stacks them (64 MiB per side for 32 pairs of 2048 x 512 fp16)
     # and uploads them on a stream of its own while this thread drives the eigensolver -- 28 ms of a 64-pair call that the first
@@ -233,6 +239,8 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
             with torch.cuda.stream(up_stream):
                 for gno_, (key_, gidx_) in enumerate(groups.items()):
                     g_ = [models[i] for i in gidx_]
+                    if isinstance(g_[0].descr1, LazySignature):
+                        continue
                     fdt_ = np.float16 if (g_[0].descr1.dtype == np.float16 and g_[0].descr2.dtype == np.float16) else np.float32
                     pair = []
                     for side in ("descr1", "descr2"):
@@ -248,8 +256,10 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
                 up_stream.synchronize()
         except BaseException as e:                      # (re-raised by the chunk's thread)
             stage_err.append(e)
-    helper = threading.Thread(target=stage_descriptors)
-    helper.start()
+    # (groups of spectral signatures have nothing to stage: no thread when every group is one)
+    helper = None if all(isinstance(models[gidx_[0]].descr1, LazySignature) for gidx_ in groups.values()) else threading.Thread(target=stage_descriptors)
+    if helper is not None:
+        helper.start()
     try:
         # ---- eigenbases: every mesh of the chunk in one batched solve (FunctionalMapping.preprocess: functional.py:300-301)
         all_meshes = [m for i in idx for m in (models[i].mesh1, models[i].mesh2)]
@@ -257,7 +267,8 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
     finally:
         if after_eigenbases is not None:
             after_eigenbases()
-        helper.join()
+        if helper is not None:
+            helper.join()
     if stage_err:
         raise stage_err[0]
     for key, gidx in groups.items():
@@ -268,8 +279,19 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
         Phi1, Phi2 = st(lambda m: m.mesh1.eigenvectors[:, :n_ev], rdt), st(lambda m: m.mesh2.eigenvectors[:, :n_ev], rdt)
         a1, a2 = st(lambda m: m.mesh1.vertex_masses, rdt), st(lambda m: m.mesh2.vertex_masses, rdt)
         lam1, lam2 = st(lambda m: m.mesh1.eigenvalues[:n_ev], np.float64), st(lambda m: m.mesh2.eigenvalues[:n_ev], np.float64)
-        fdt, F1d, F2d = staged[key]
-        F1d.record_stream(main_stream); F2d.record_stream(main_stream)
+        if isinstance(g[0].descr1, LazySignature):
+            # HKS / WKS of the group's meshes, one call per side (FunctionalMapping.preprocess(signature_route="device"): the same
+            # float64 values, rounded to the fit's fp32 on the device instead of downloaded and converted)
+            sig = g[0].descr1
+            own = lambda m: np.asarray(m.eigenvectors).dtype
+            E1 = Phi1 if own(g[0].mesh1) == rdt else st(lambda m: m.mesh1.eigenvectors[:, :n_ev], own(g[0].mesh1))
+            E2 = Phi2 if own(g[0].mesh2) == rdt else st(lambda m: m.mesh2.eigenvectors[:, :n_ev], own(g[0].mesh2))
+            fdt = np.float32
+            F1d = eng.signatures(E1, lam1, sig.kind, sig.num, out_dtype=torch.float32)
+            F2d = eng.signatures(E2, lam2, sig.kind, sig.num, out_dtype=torch.float32)
+        else:
+            fdt, F1d, F2d = staged[key]
+            F1d.record_stream(main_stream); F2d.record_stream(main_stream)
         # ---- fit (FunctionalMapping.fit: the fp32 view of the bases like the reference's fit, functional.py:412-413)
         dev = {"Phi1": eng._dev(Phi1.astype(np.float32), torch.float32, "Phi1"), "Phi2": eng._dev(Phi2.astype(np.float32), torch.float32, "Phi2"),
                "a1": eng._dev(a1.astype(np.float32), torch.float32, "a1"), "a2": eng._dev(a2.astype(np.float32), torch.float32, "a2"),
@@ -412,9 +434,10 @@ def compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev=50, compute_e
 
 def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_extra, optimizer, descr_type, maxiter, optimize_p2p, fit_params, streams):
     import torch
-    assert descr_type == "neural", "the batched call takes network descriptors (descr_type='neural')"
+    assert descr_type in ["neural", "HKS", "WKS"]
     B = len(meshes1_t)
-    assert len(meshes2_t) == B and len(c1s) == B and len(c2s) == B
+    spectral = descr_type != "neural"           # (c1s, c2s may be None then: the signatures come from the meshes, functional_map.py:19-35)
+    assert len(meshes2_t) == B and (spectral or (len(c1s) == B and len(c2s) == B))
     fit_params = dict(fit_params or {})
     fit_params.pop("verbose", None)
     known = {"w_descr", "w_lap", "w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal", "optinit",
@@ -439,7 +462,12 @@ def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_ext
         m2 = TriMesh(_np(meshes2_t[i].verts_list()[0]), _np(meshes2_t[i].faces_list()[0]))
         model = FunctionalMapping(m1, m2, partial=False, optimizer=optimizer)
         model.k1, model.k2 = n_ev, n_ev
-        model.descr1, model.descr2 = _np(c1s[i]), _np(c2s[i])
+        if spectral:
+            from .pyFM.signatures import LazySignature
+            num = 16 if descr_type == "HKS" else 2048                          # compute_surface_map's sizes
+            model.descr1, model.descr2 = LazySignature(model.mesh1, descr_type, num, n_ev), LazySignature(model.mesh2, descr_type, num, n_ev)
+        else:
+            model.descr1, model.descr2 = _np(c1s[i]), _np(c2s[i])
         models.append(model)
     out = [None] * B
     if streams is None:

@@ -103,7 +103,12 @@ class FunctionalMapping:
 
     # ---------------------------------------------------------------- preprocess (functional.py:264-350)
     def preprocess(self, n_ev=(50, 50), n_descr=100, descr_type='WKS', landmarks=None, subsample_step=1, k_process=None,
-                   verbose=False, descr1=None, descr2=None):
+                   verbose=False, descr1=None, descr2=None, signature_route="host"):
+        """signature_route (not in the reference): where descr_type 'HKS' / 'WKS' is evaluated.  "host" (default): the NumPy mirror
+        of the reference, pyFM/signatures.py; "device": MatchEngine.signatures, the [plain | landmark] blocks of both meshes in one
+        call, downloaded as NumPy float64 (equal to the host's up to the summation order and the device's exp)."""
+        if signature_route not in ("host", "device"):
+            raise ValueError(f'signature_route must be "host" or "device", not {signature_route!r}')
         self.k1, self.k2 = n_ev
         if k_process is None:
             k_process = 1
@@ -119,6 +124,8 @@ class FunctionalMapping:
             lmks1, lmks2 = self._get_lmks(landmarks)
         if descr1 is not None and descr2 is not None:
             self.descr1, self.descr2 = descr1, descr2
+        elif descr_type in ('HKS', 'WKS') and signature_route == "device":
+            self.descr1, self.descr2 = self._signatures_device(descr_type, n_descr, (lmks1, lmks2) if use_lm else None)
         elif descr_type in ('HKS', 'WKS'):                                       # functional.py:308-329
             sig = sg.mesh_HKS if descr_type == 'HKS' else sg.mesh_WKS
             self.descr1 = sig(self.mesh1, n_descr, k=self.k1)                    # (N1, n_descr)
@@ -132,6 +139,28 @@ class FunctionalMapping:
             self.descr1 = self.descr1[:, np.arange(0, self.descr1.shape[1], subsample_step)]      # functional.py:333-334
             self.descr2 = self.descr2[:, np.arange(0, self.descr2.shape[1], subsample_step)]
         return self                                                                          # no normalisation (:336-344)
+
+    def _signatures_device(self, descr_type, n_descr, lmks):
+        """[plain | landmark blocks] of both meshes (functional.py:308-329) from one device call when the two use the same number of
+        eigenpairs (the smaller mesh padded with rows that are not read), else one call per mesh"""
+        from ..engine import default_engine
+        eng = default_engine()
+        sides = []
+        for mesh, kk in ((self.mesh1, self.k1), (self.mesh2, self.k2)):
+            assert mesh.eigenvalues is not None, "Eigenvalues should be processed"
+            kk = min(kk, len(mesh.eigenvalues))
+            sides.append((np.asarray(mesh.eigenvectors)[:, :kk], np.asarray(mesh.eigenvalues, dtype=np.float64)[:kk]))
+        lm = None if lmks is None else [np.asarray(l).reshape(-1) for l in lmks]
+        if sides[0][0].shape[1] == sides[1][0].shape[1] and sides[0][0].dtype == sides[1][0].dtype:
+            n = [s_[0].shape[0] for s_ in sides]
+            Phi = np.zeros((2, max(n), sides[0][0].shape[1]), dtype=sides[0][0].dtype)
+            for q in range(2):
+                Phi[q, :n[q]] = sides[q][0]
+            S = eng.signatures(Phi, np.stack([s_[1] for s_ in sides]), descr_type, n_descr, landmarks=None if lm is None else np.stack(lm),
+                               plain=True, n_verts=n).cpu().numpy()
+            return S[0, :n[0]], S[1, :n[1]]
+        return tuple(eng.signatures(sides[q][0][None], sides[q][1][None], descr_type, n_descr, landmarks=None if lm is None else lm[q][None],
+                                    plain=True)[0].cpu().numpy() for q in range(2))
 
     # ---------------------------------------------------------------- fit (functional.py:352-487)
     def fit(self, w_descr=1e-1, w_lap=1e-3, w_dcomm=1, w_orient=0, w_area=0, w_conformal=0, w_p2p=0, w_stochastic=0, w_ent=0,

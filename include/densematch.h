@@ -569,6 +569,29 @@ int dm_graph_geodesic(dm_ctx* ctx, int B, int N, int nnz, const int32_t* cols, c
 int dm_fps_graph(dm_ctx* ctx, int B, int N, int nnz, const int32_t* cols, const double* w, const int32_t* n_verts /*nullable*/,
                  int size, const int32_t* start, int32_t* out, int32_t* info);
 
+/* ---- heat / wave kernel signatures -------------------------------------------------
+ * The spectral descriptors of FunctionalMapping.preprocess (reference functional.py:308-334; HKS_functions.py:73,97-98,
+ * WKS_functions.py:29,71,118-126), scaled form, for B meshes padded to N vertices (n_verts: HOST array (B), nullable = all N):
+ *   plain block       S[n, t]   = (sum_k w[t,k] Phi[n,k]^2)        * (1 / sum_k w[t,k])
+ *   landmark block p  S_p[n, t] = (sum_k w[t,k] Phi[p,k] Phi[n,k]) * (1 / sum_k w[t,k])
+ *   kind 0 (HKS): w[t,k] = exp(-(t[t] mu[k]))      kind 1 (WKS): w[t,k] = exp(-((t[t] - mu[k]) (t[t] - mu[k])) / denom)
+ * over the eigen-columns k0 <= k < K of Phi (B,N,ld).  The table is prepared on the host (pyFM/signatures.py: signature_tables):
+ *   t (B,T) fp64 DEVICE: times / energies;  mu (B,K) fp64 DEVICE: sorted |lambda| (HKS), their logarithms (WKS; entries before k0
+ *   are never read);  denom (B) fp64 DEVICE: 2 sigma^2 (WKS; nullable for HKS);  k0 (B,2) int32 HOST: first column kept by the plain
+ *   block and by the landmark blocks (WKS drops lambda <= 1e-5 / <= 1e-2);  landmarks (B,P) int32 HOST, P >= 0;  plain 0 | 1.
+ * out (B, N, (plain + P) T), fp64 or (out_f32) fp32 rounded once from the fp64 value; columns [plain | p0 | p1 | ...], T each; rows
+ * past n_verts are 0.  Every operation in the argument of exp is rounded on its own, so the arguments are the host's bits; a column
+ * whose weights all underflow comes out NaN in every row (0 * inf), as in the reference.  A mesh's result does not depend on the
+ * other meshes of the call.  DM_EINVAL: T < 1, k0 >= K for a block kind in use, a landmark outside [0, n_verts), plain + P = 0. */
+int dm_spectral_signatures(dm_ctx* ctx, int B, int N, const int32_t* n_verts /*host, nullable*/, int K, const float* Phi, int ld,
+                           int kind, int T, const double* t, const double* mu, const double* denom /*nullable for HKS*/,
+                           const int32_t* k0 /*host*/, int P, const int32_t* landmarks /*host, nullable when P = 0*/, int plain,
+                           int out_f32, void* out);
+int dm_spectral_signatures_f64(dm_ctx* ctx, int B, int N, const int32_t* n_verts /*host, nullable*/, int K, const double* Phi, int ld,
+                               int kind, int T, const double* t, const double* mu, const double* denom /*nullable for HKS*/,
+                               const int32_t* k0 /*host*/, int P, const int32_t* landmarks /*host, nullable when P = 0*/, int plain,
+                               int out_f32, void* out);
+
 /* ---- spectral ICP -------------------------------------------------------------
  * nit times: p21 = knn21(C); Chat = argmin |Phi2[:, :k2] X - Phi1[p21, :k1]|_F (no mass);
  * C = U eye(k2,k1) V^T with U S V^T = svd(Chat), i.e. the orthogonal polar factor of Chat.
