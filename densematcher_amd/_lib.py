@@ -46,6 +46,7 @@ SIGNATURES = {
     "dm_fmap_fit_fused_ok": (_i, [_i, _i, _p, _i]),
     "dm_fmap_fit_fused": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _i, _p, _d, _d, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dm_fmap_descr_ops": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
+    "dm_fmap_orient_ops": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _i, _p]),
     "dm_fm_to_p2p": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
     "dm_fm_to_p2p_uses_split": (_i, [_p, _i, _i, _i]),
     "dm_knn_query_f64": (_i, [_p, _i, _i, _i, _i, _p, _p, _p]),
@@ -79,7 +80,7 @@ SIGNATURES = {
 
 # the float64-basis forms (const double* Phi / mass): same argument lists
 for _n in ("dm_project", "dm_fmap_fit", "dm_fmap_c00", "dm_fm_to_p2p", "dm_mapped_indicator", "dm_p2p_to_fm", "dm_precise_map", "dm_p2p_to_fm_lstsq", "dm_icp", "dm_lsa_indicator",
-           "dm_zoomout", "dm_zoomout_sub", "dm_spectral_signatures"):
+           "dm_zoomout", "dm_zoomout_sub", "dm_spectral_signatures", "dm_fmap_orient_ops"):
     SIGNATURES[_n + "_f64"] = SIGNATURES[_n]
 
 _libs = {}

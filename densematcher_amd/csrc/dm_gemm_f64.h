@@ -31,8 +31,12 @@ template <class T, class = void> struct dm_elem { typedef double type; };
 template <class T> struct dm_elem<T, std::void_t<typename T::elem_t>> { typedef typename T::elem_t type; };
 typedef __attribute__((address_space(1))) const f32x4 dm_gf32x4;      // global address space: global_load, not flat_load
 // TN form: a functor may define raw_t + load4raw / cvt / zero (same idea); otherwise load4 delivers doubles directly.
+// pre_t (optional, next to raw_t): what pre() hands to load4raw when one int is not enough (the three vertices of a face, dm_orient.hip)
+template <class T, class = void> struct dm_tn_pre { typedef int type; };
+template <class T> struct dm_tn_pre<T, std::void_t<typename T::pre_t>> { typedef typename T::pre_t type; };
 template <class T, class = void> struct dm_tn_raw {
     struct type { double v[4]; };
+    typedef int pre_t;
     static __device__ __forceinline__ int pre(const T&, int, int) { return 0; }
     static __device__ __forceinline__ void load(const T& op, int b, int n, int col0, int, type& r) { op.load4(b, n, col0, r.v); }
     static __device__ __forceinline__ void zero(type& r) { r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.0; }
@@ -41,8 +45,9 @@ template <class T, class = void> struct dm_tn_raw {
 template <class T> struct dm_tn_raw<T, std::void_t<typename T::raw_t>> {
     typedef typename T::raw_t type;
     // pre(): a value the row's load depends on (a gather index), fetched one stage earlier than the row itself
-    static __device__ __forceinline__ int pre(const T& op, int b, int n) { return op.pre(b, n); }
-    static __device__ __forceinline__ void load(const T& op, int b, int n, int col0, int pv, type& r) { op.load4raw(b, n, col0, pv, r); }
+    typedef typename dm_tn_pre<T>::type pre_t;
+    static __device__ __forceinline__ pre_t pre(const T& op, int b, int n) { return op.pre(b, n); }
+    static __device__ __forceinline__ void load(const T& op, int b, int n, int col0, const pre_t& pv, type& r) { op.load4raw(b, n, col0, pv, r); }
     static __device__ __forceinline__ void zero(type& r) { T::zero(r); }
     static __device__ __forceinline__ void cvt(const type& r, double (&v)[4]) { T::cvt(r, v); }
 };
@@ -240,7 +245,8 @@ __global__ __launch_bounds__(256) void gemm_tn_f64(OpX opx, OpY opy, Out out, in
     typename dm_tn_raw<OpX>::type rxa, rxb;
     typename dm_tn_raw<OpY>::type rya, ryb;
     // (macros, not lambdas: by-reference lambda captures of the staging arrays end up in scratch)
-    int px = 0, py = 0;
+    typename dm_tn_raw<OpX>::pre_t px{};
+    typename dm_tn_raw<OpY>::pre_t py{};
 #define TN_PRE(s_)                                                              \
     {                                                                           \
         const int n_ = kbeg + (s_) * TN_BK + lrow;                              \

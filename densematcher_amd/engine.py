@@ -319,6 +319,55 @@ class MatchEngine:
                                              _lib.DM_F16 if fdt == torch.float16 else _lib.DM_F32, _ptr(ops)))
         return ops
 
+    def orientation_ops(self, verts, faces, Phi, F, k=None, row_scale=None, n_faces=None):
+        """Orientation operators of the descriptors in the reduced basis -> (B,D,k,k) f64 on the device: per descriptor p
+        pinv diag(1 / area) W_p Phi with W_p the sparse operator g -> <n x grad f_p, grad g> (reference geometry.py:919-985; what
+        FunctionalMapping.compute_orientation_op assembles per descriptor on the host).  All descriptors of a mesh are one float64
+        matrix-core product (dm_fmap_orient_ops); a mesh's result does not depend on the batch it is in.
+        verts (B,N,3) f64, faces (B,M,3) integer, Phi (B,N,ld) f32 | f64 (the first k columns are used), F (B,N,D) f16 | f32.
+        row_scale (B,N) f64: the rows of the left factor are row_scale * Phi -- mass / vertex_areas gives compute_orientation_op's
+        operators (area="vertex"), None (ones) those of area="mass", which energy_func_std builds (base_functions.py:567-597).
+        n_faces (B): meshes with fewer faces are padded to M rows; rows beyond n_faces[b] are not read as faces.
+        A face index outside [0, N) is a ValueError, checked on the host before anything is uploaded."""
+        import numpy as np
+        fh = faces.cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+        if fh.ndim != 3 or fh.shape[2] != 3 or fh.shape[1] == 0 or not np.issubdtype(fh.dtype, np.integer):
+            raise ValueError("orientation_ops: faces must be (B, M, 3) integers")
+        B, M = fh.shape[:2]
+        sfx, Phi = self._reals(Phi)
+        if Phi.dim() != 3 or Phi.shape[0] != B:
+            raise ValueError("orientation_ops: Phi must be (B, N, ld)")
+        _, N, ld = Phi.shape
+        k = ld if k is None else int(k)
+        nf = None
+        if n_faces is not None:
+            nf = np.ascontiguousarray(np.asarray(n_faces).reshape(-1), dtype=np.int32)
+            if nf.shape != (B,) or nf.min() < 0 or nf.max() > M:
+                raise ValueError(f"orientation_ops: n_faces must be (B,) counts in [0, {M}]")
+        used = fh if nf is None else fh[np.arange(M)[None, :] < nf[:, None]]
+        if used.size and (used.min() < 0 or used.max() >= N):
+            raise ValueError(f"orientation_ops: face index outside [0, {N})")
+        verts = self._dev(verts, torch.float64, "verts")
+        if verts.shape != (B, N, 3):
+            raise ValueError("orientation_ops: verts must be (B, N, 3) for the N rows of Phi")
+        faces_d = self._dev(np.ascontiguousarray(fh, dtype=np.int32), torch.int32, "faces")
+        if not isinstance(F, torch.Tensor):
+            F = torch.as_tensor(F)
+        fdt = torch.float16 if F.dtype == torch.float16 else torch.float32
+        F = self._dev(F, fdt, "F")
+        if F.dim() != 3 or F.shape[:2] != (B, N):
+            raise ValueError("orientation_ops: F must be (B, N, D)")
+        D = F.shape[2]
+        if row_scale is not None:
+            row_scale = self._dev(row_scale, torch.float64, "row_scale")
+            if row_scale.shape != (B, N):
+                raise ValueError("orientation_ops: row_scale must be (B, N)")
+        ops = torch.empty((B, D, k, k), dtype=torch.float64, device=self.device)
+        fn = getattr(self.lib, "dm_fmap_orient_ops" + sfx)
+        self._chk(fn(self.ctx, B, N, M, D, k, _ptr(verts), _ptr(faces_d), None if nf is None else nf.ctypes.data_as(C.c_void_p), _ptr(Phi), ld,
+                     _ptr(row_scale), _ptr(F), _lib.DM_F16 if fdt == torch.float16 else _lib.DM_F32, _ptr(ops)))
+        return ops
+
     def energy_grad(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
         """Energy (B,) and gradient (B,k2,k1) of the functional-map objective for the weights in `weights` (dict with keys
         of WEIGHT_ORDER; reference energy_func_std / grad_energy_std, base_functions.py:480-763)."""
@@ -383,18 +432,30 @@ class MatchEngine:
         Bm = self.project(Phi2, batch["a2"], batch["F2"], k2)
         lam1 = self._dev(batch["lam1"], torch.float64, "lam1")[:, :k1].contiguous()
         lam2 = self._dev(batch["lam2"], torch.float64, "lam2")[:, :k2].contiguous()
+        import numpy as np
         w = {n: float(v) for n, v in weights.items() if n != "w_orient"}
-        w_orient, w_dcomm = float(weights.get("w_orient", 0.0)), float(weights.get("w_dcomm", 0.0))
+        # w_orient: one weight for the batch, or (B,) -- every pair of a batched fit has its own rescaled weight (functional.py:448-456)
+        w_orient = np.asarray(weights.get("w_orient", 0.0), dtype=np.float64)
+        w_dcomm = float(weights.get("w_dcomm", 0.0))
+        if w_orient.ndim > 1:
+            raise ValueError("w_orient must be a number or (B,) weights")
         ops1 = ops2 = None
         if w_dcomm > 0:
             ops1 = self.descr_ops(Phi1, batch["a1"], batch["F1"], k1)
             ops2 = self.descr_ops(Phi2, batch["a2"], batch["F2"], k2)
-        if w_orient > 0:
+        if (w_orient > 0).any():
             if orient_ops is None:
                 raise ValueError("w_orient > 0 needs the orientation operators (FunctionalMapping.compute_orientation_op)")
-            sc = (w_orient / w_dcomm) ** 0.5 if w_dcomm > 0 else w_orient ** 0.5
-            o1 = self._dev(orient_ops[0], torch.float64, "orient_ops1") * sc
-            o2 = self._dev(orient_ops[1], torch.float64, "orient_ops2") * sc
+            scale = lambda wo: (wo / w_dcomm) ** 0.5 if w_dcomm > 0 else wo ** 0.5
+            o1 = self._dev(orient_ops[0], torch.float64, "orient_ops1")
+            o2 = self._dev(orient_ops[1], torch.float64, "orient_ops2")
+            if w_orient.ndim == 0:
+                sc = scale(float(w_orient))
+            else:                                       # (per pair the same float64 product as the scalar form)
+                if w_orient.shape[0] != o1.shape[0]:
+                    raise ValueError("w_orient: one weight per pair of the batch")
+                sc = torch.tensor([scale(max(float(wo), 0.0)) for wo in w_orient], dtype=torch.float64, device=self.device).view(-1, 1, 1, 1)
+            o1, o2 = o1 * sc, o2 * sc
             ops1 = o1 if ops1 is None else torch.cat([ops1, o1], dim=1).contiguous()
             ops2 = o2 if ops2 is None else torch.cat([ops2, o2], dim=1).contiguous()
             if w_dcomm <= 0:

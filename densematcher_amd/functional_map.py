@@ -298,16 +298,29 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
                "lam1": eng._dev(lam1, torch.float64, "lam1"), "lam2": eng._dev(lam2, torch.float64, "lam2"),
                "F1": eng._dev(F1d, tdt[fdt], "F1"), "F2": eng._dev(F2d, tdt[fdt], "F2")}
         fp = dict(w_descr=1e-1, w_lap=1e-3, w_dcomm=1, w_p2p=0, w_stochastic=0, w_ent=0, w_range01=0, w_sumto1=0, w_area=0, w_conformal=0,
-                  optinit="zeros", maxiter=1000000, stopping="reference")
+                  optinit="zeros", maxiter=1000000, stopping="reference", w_orient=0, orient_reversing=False, orient_route="device")
         fp.update({k_: v for k_, v in fit_params.items() if k_ in fp})
         general = {n: fp[n] for n in ("w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal")}
         from .pyFM.functional import CLOSED_FORM_MAX_K1
         wide = n_ev > CLOSED_FORM_MAX_K1              # (FunctionalMapping.fit: maps wider than the closed form's solvers take the iterative scheme, tight)
-        if any(v > 0 for v in general.values()) or wide:
+        if any(v > 0 for v in general.values()) or fp["w_orient"] > 0 or wide:
             from .pyFM.functional import LBFGS_OPTIONS, LBFGS_WIDE
             x0 = np.stack([m.get_x0(optinit=fp["optinit"]) for m in g])
-            C0, res = eng.fit_general(dev, dict(w_descr=fp["w_descr"], w_lap=fp["w_lap"], **general), x0, maxiter=fp["maxiter"],
-                                      lbfgs_options=LBFGS_WIDE if wide else (LBFGS_OPTIONS if fp["stopping"] == "tight" else None))
+            weights = dict(w_descr=fp["w_descr"], w_lap=fp["w_lap"], **general)
+            orient_ops = None
+            if fp["w_orient"] > 0:
+                # FunctionalMapping.fit's rescaling (functional.py:432-456) for the whole group: the operators of both forms, the two
+                # energies at x0, then every pair's own weight
+                (o1, o2), orient_ops = _group_orientation_ops(eng, g, (Phi1, Phi2), (dev["F1"], dev["F2"]), n_ev, fp["orient_route"], fp["orient_reversing"])
+                e_native = eng.fit_energy(dev, dict(weights, w_orient=0.0), x0)
+                e_orient = eng.fit_energy(dev, dict(w_orient=1.0), x0, orient_ops=(o1, o2))
+                w_orient = [fp["w_orient"] * float(e_native[q]) / float(e_orient[q]) for q in range(nb)]
+                for q, m in enumerate(g):
+                    m.w_orient_rescaled = w_orient[q]
+                weights["w_orient"] = np.asarray(w_orient, dtype=np.float64)
+            C0, res = eng.fit_general(dev, weights, x0, maxiter=fp["maxiter"],
+                                      lbfgs_options=LBFGS_WIDE if wide else (LBFGS_OPTIONS if fp["stopping"] == "tight" else None),
+                                      orient_ops=orient_ops)
             C0 = np.asarray(C0, dtype=np.float64)
         else:
             res = None
@@ -408,6 +421,38 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
                       h["knn21"][q], h["knn12"][q], hi["knn21"][q], hi["knn12"][q])
 
 
+def _group_orientation_ops(eng, g, Phis, Fs, n_ev, route, reversing):
+    """the orientation operators of a group of models, both forms FunctionalMapping.fit uses: ((o1, o2) the rescaling operators -- rows
+    divided by vertex_areas, the second reversed on request --, (f1, f2) those of the optimisation -- rows divided by diag(A), never
+    reversed), each (nb, D, k, k).  Phis: the stacked bases in the meshes' own precision (what the single call's device route reads), Fs: the
+    descriptors as staged for the fit.  route "device": MatchEngine.orientation_ops on the stacked meshes (mesh 2's face count may
+    differ inside a group: padded, n_faces), the operators stay on the device; "host": the per-pair host operators, stacked."""
+    from .pyFM.functional import _orient_row_scale
+    if route == "host":
+        st = lambda ops, side: np.stack([np.stack([o[side] for o in ops_q]) for ops_q in ops])
+        resc = [m.compute_orientation_op(reversing=reversing) for m in g]
+        fit = [m.compute_orientation_op(reversing=False, area="mass") for m in g]
+        return (st(resc, 0), st(resc, 1)), (st(fit, 0), st(fit, 1))
+    vertex, same = [], True
+    for side, (Phi, F) in enumerate(zip(Phis, Fs)):
+        meshes = [(m.mesh1, m.mesh2)[side] for m in g]
+        verts = np.stack([np.asarray(m.vertlist, dtype=np.float64) for m in meshes])
+        nf = np.array([m.facelist.shape[0] for m in meshes], dtype=np.int32)
+        faces = np.zeros((len(meshes), int(nf.max()), 3), dtype=np.int32)
+        for q, m in enumerate(meshes):
+            faces[q, :nf[q]] = m.facelist
+        rs = [_orient_row_scale(m) for m in meshes]
+        scale = None
+        if any(r is not None for r in rs):
+            same = False
+            scale = np.stack([np.ones(m.n_vertices) if r is None else r for m, r in zip(meshes, rs)])
+        vertex.append((eng.orientation_ops(verts, faces, Phi, F, k=n_ev, row_scale=scale, n_faces=nf), (verts, faces, Phi, F, nf)))
+    (r1, _), (r2, _) = vertex
+    # (lumped masses ARE the vertex areas -- A diagonal: the two forms are the same operators, one call serves both)
+    fit = (r1, r2) if same else tuple(eng.orientation_ops(v, f, P, F, k=n_ev, n_faces=nf) for _, (v, f, P, F, nf) in vertex)
+    return (r1, -r2 if reversing else r2), fit
+
+
 def compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev=50, compute_extra=False, optimizer="fmin_l_bfgs_b", descr_type="neural",
                               maxiter=100000, optimize_p2p=False, fit_params=None, streams=None, robust_backend=None):
     """compute_surface_map for a list of mesh pairs: returns the list of the 14-tuples compute_surface_map returns, each equal to the
@@ -442,15 +487,14 @@ def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_ext
     fit_params.pop("verbose", None)
     known = {"w_descr", "w_lap", "w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal", "optinit",
              "maxiter", "stopping", "w_orient", "w_area_difference", "w_mumford_shah", "mumford_shah_var", "w_eta_entropy", "orient_reversing",
-             "device", "driver"}
+             "orient_route", "device", "driver"}
     unknown = set(fit_params) - known
     if unknown:
         raise TypeError(f"fit() got unexpected keyword arguments {sorted(unknown)}")
     if any(fit_params.get(n, 0) > 0 for n in ("w_area_difference", "w_mumford_shah", "w_eta_entropy")):
         raise NotImplementedError("area-difference / Mumford-Shah / eta-entropy terms are not on the accelerated path; pass 0")
-    if fit_params.get("w_orient", 0) > 0:
-        raise NotImplementedError("w_orient: the orientation operators are built per pair on the host (FunctionalMapping.fit); "
-                                  "use compute_surface_map for it")
+    if fit_params.get("orient_route", "device") not in ("host", "device"):
+        raise ValueError(f'orient_route must be "host" or "device", not {fit_params["orient_route"]!r}')
     if fit_params.get("stopping", "reference") not in ("tight", "reference"):
         raise ValueError("stopping must be 'tight' or 'reference'")
     timing = os.environ.get("TIMEIT", False)

@@ -5,6 +5,7 @@ matching hot path uses.  Arithmetic: libdensematch (HIP) through densematcher_am
 import copy
 
 import numpy as np
+from scipy import sparse
 
 from . import refine, signatures as sg, spectral
 
@@ -23,6 +24,16 @@ CLOSED_FORM_MAX_K1 = 200          # dm_fmap_solve / dm_fmap_fit: the in-LDS solv
 LBFGS_OPTIONS = {"ftol": 1e-12, "gtol": 1e-9, "maxcor": 30, "maxfun": 15000}
 # maps wider than the closed form takes (quadratic energy, k^2 > 40 000 unknowns): run until the gradient test or the line search's noise floor
 LBFGS_WIDE = {"ftol": 1e-15, "gtol": 1e-11, "maxcor": 30, "maxfun": 50000}
+
+
+def _orient_row_scale(mesh):
+    """mass / vertex_areas, the row scale that turns Phi into the left factor of compute_orientation_op's operators (pinv = Phi^T A, rows
+    divided by vertex_areas); None where it is 1 everywhere (TriMesh: the row sums of a lumped A are its diagonal), i.e. the "mass" form"""
+    mass = np.asarray(mesh.A.diagonal(), dtype=np.float64)
+    if (mesh.A - sparse.diags(mesh.A.diagonal())).count_nonzero() != 0:
+        raise NotImplementedError("the device route of the orientation operators takes a lumped (diagonal) mass matrix; use the host route")
+    va = np.asarray(mesh.vertex_areas, dtype=np.float64)
+    return None if np.array_equal(mass, va) else mass / va
 
 
 class FunctionalMapping:
@@ -165,7 +176,8 @@ class FunctionalMapping:
     # ---------------------------------------------------------------- fit (functional.py:352-487)
     def fit(self, w_descr=1e-1, w_lap=1e-3, w_dcomm=1, w_orient=0, w_area=0, w_conformal=0, w_p2p=0, w_stochastic=0, w_ent=0,
             w_range01=0, w_sumto1=0, w_area_difference=0, w_mumford_shah=0, mumford_shah_var=0.1, w_eta_entropy=0,
-            orient_reversing=False, optinit='zeros', verbose=False, maxiter=1000000, device=None, stopping="reference", driver="device"):
+            orient_reversing=False, optinit='zeros', verbose=False, maxiter=1000000, device=None, stopping="reference", driver="device",
+            orient_route="host"):
         """reference functional.py:352-487.  With only w_descr / w_lap > 0 the minimiser (what the reference's L-BFGS-B
         converges to, first column pinned) is obtained in closed form on the GPU.  With any of
         w_dcomm, w_orient, w_area, w_conformal, w_p2p, w_stochastic, w_ent, w_range01, w_sumto1 > 0 the reference's own scheme
@@ -175,8 +187,15 @@ class FunctionalMapping:
         Only the area-difference, Mumford-Shah and eta-entropy terms are not on the path (NotImplementedError).
         stopping = "reference" (default): SciPy's default rule, i.e. what the reference's call runs with (ftol 2.2e-9, gtol 1e-5):
         the fit ends where the reference's ends, a few 1e-4 short of the minimiser, and the drop-in agrees best with the
-        reference's own outputs (INTEGRATION.md has the per-slot table); "tight": ftol 1e-12, the float64 minimiser to 1e-5."""
+        reference's own outputs (INTEGRATION.md has the per-slot table); "tight": ftol 1e-12, the float64 minimiser to 1e-5.
+        orient_route (not in the reference; read when w_orient > 0): "host" (default) builds the orientation operators with
+        compute_orientation_op's sparse products per descriptor, as the reference does; "device" builds both operator sets
+        (rescaling and optimisation) with MatchEngine.orientation_ops and keeps them on the device until the fit has read them.
+        The device route reads the descriptors the fit itself reads (fp16 / fp32): for float64 descriptors that are not fp32
+        numbers its operators differ from the host route's at 1e-7 relative."""
         from ..engine import default_engine
+        if orient_route not in ("host", "device"):
+            raise ValueError(f'orient_route must be "host" or "device", not {orient_route!r}')
         if optinit not in ['random', 'identity', 'zeros']:
             raise ValueError(f"optinit arg should be 'random', 'identity' or 'zeros', not {optinit}")
         if self.optimizer not in _OPTIMIZERS:
@@ -225,17 +244,26 @@ class FunctionalMapping:
                 # (orientation energy at x0).  The reference rescales with the NumPy operators of compute_orientation_op
                 # (reversing honoured there) and then OPTIMISES with the operators energy_func_std rebuilds itself
                 # (base_functions.py:567-597: rows divided by diag(A), never reversed) -- both restated as they are.
-                resc = self.compute_orientation_op(reversing=orient_reversing)
-                o1 = np.stack([a for a, _ in resc])[None]
-                o2 = np.stack([b for _, b in resc])[None]
+                if orient_route == "device":
+                    r1, r2 = self._orientation_ops_device("vertex")
+                    o1, o2 = r1, (-r2 if orient_reversing else r2)
+                else:
+                    resc = self.compute_orientation_op(reversing=orient_reversing)
+                    o1 = np.stack([a for a, _ in resc])[None]
+                    o2 = np.stack([b for _, b in resc])[None]
                 w_native = dict(weights, w_orient=0.0)
                 e_native = eng.fit_energy(dev, w_native, x0[None])
                 e_orient = eng.fit_energy(dev, dict(w_orient=1.0), x0[None], orient_ops=(o1, o2))
                 w_orient = w_orient * float(e_native[0]) / float(e_orient[0])
                 weights["w_orient"] = w_orient
                 self.w_orient_rescaled = w_orient
-                fit_ops = self.compute_orientation_op(reversing=False, area="mass")
-                orient_ops = (np.stack([a for a, _ in fit_ops])[None], np.stack([b for _, b in fit_ops])[None])
+                if orient_route == "device":
+                    # (lumped masses ARE the vertex areas -- A diagonal: the two forms are the same operators, one call serves both)
+                    same = all(_orient_row_scale(m) is None for m in (m1, m2))
+                    orient_ops = (r1, r2) if same else self._orientation_ops_device("mass")
+                else:
+                    fit_ops = self.compute_orientation_op(reversing=False, area="mass")
+                    orient_ops = (np.stack([a for a, _ in fit_ops])[None], np.stack([b for _, b in fit_ops])[None])
             self._verbose_terms(eng, dev, weights, x0, orient_ops, "x0")
             C, res = eng.fit_general(dev, weights, x0[None], maxiter=maxiter,
                                      lbfgs_options=(LBFGS_WIDE if wide else LBFGS_OPTIONS) if stopping == "tight" else None, driver=driver,
@@ -275,11 +303,21 @@ class FunctionalMapping:
                 e = eng.fit_energy(dev, {name: w}, np.asarray(x)[None], orient_ops=orient_ops if name == "w_orient" else None)
                 print(label, float(e[0]))
 
-    def compute_orientation_op(self, reversing=False, normalize=False, area="vertex"):
+    def compute_orientation_op(self, reversing=False, normalize=False, area="vertex", route="host"):
         """functional.py:686-728: per descriptor the pair (pinv1 O1 Phi1, +-pinv2 O2 Phi2) of orientation operators in the reduced
         bases, O = TriMesh.orientation_op(gradient of the descriptor).  area = "vertex": rows divided by the mesh's vertex_areas (the
-        reference's method); "mass": by diag(A) (what energy_func_std builds, base_functions.py:573).  Host arithmetic (sparse
-        products per descriptor), as in the reference."""
+        reference's method); "mass": by diag(A) (what energy_func_std builds, base_functions.py:573).
+        route (not in the reference) = "host" (default): sparse products per descriptor, as in the reference; "device": all descriptors
+        of a mesh in one float64 matrix-core product (MatchEngine.orientation_ops), the same list downloaded.  The device route reads
+        the descriptors as the fit stages them (fp16 when both sets are fp16, else fp32): float64 descriptors that are not fp32 numbers
+        give operators that differ from the host route's at 1e-7 relative.  normalize=True is host-only."""
+        if route not in ("host", "device"):
+            raise ValueError(f'route must be "host" or "device", not {route!r}')
+        if route == "device":
+            if normalize:
+                raise NotImplementedError('compute_orientation_op(normalize=True) is not on the device route; use route="host"')
+            o1, o2 = (o[0].cpu().numpy() for o in self._orientation_ops_device(area))
+            return [(a, -b if reversing else b) for a, b in zip(o1, o2)]
         out = []
         sides = []
         for mesh, descr, k in ((self.mesh1, self.descr1, self.k1), (self.mesh2, self.descr2, self.k2)):
@@ -292,6 +330,24 @@ class FunctionalMapping:
         for a, b in zip(*sides):
             out.append((a, -b if reversing else b))
         return out
+
+    def _orientation_ops_device(self, area):
+        """the orientation operators of both meshes as device tensors (1, D, k1, k1), (1, D, k2, k2), never reversed"""
+        from ..engine import default_engine
+        from .spectral.convert import _real_dtype
+        if area not in ("vertex", "mass"):
+            raise ValueError(f'area must be "vertex" or "mass", not {area!r}')
+        eng = default_engine()
+        d1, d2 = np.asarray(self.descr1), np.asarray(self.descr2)
+        fdt = np.float16 if (d1.dtype == np.float16 and d2.dtype == np.float16) else np.float32      # (the dtype fit() stages)
+        rdt = _real_dtype(self.mesh1.eigenvectors, self.mesh2.eigenvectors)
+        out = []
+        for mesh, descr, k in ((self.mesh1, d1, self.k1), (self.mesh2, d2, self.k2)):
+            rs = _orient_row_scale(mesh) if area == "vertex" else None
+            out.append(eng.orientation_ops(np.asarray(mesh.vertlist, dtype=np.float64)[None], np.asarray(mesh.facelist)[None],
+                                           np.ascontiguousarray(np.asarray(mesh.eigenvectors)[:, :k], dtype=rdt)[None],
+                                           np.ascontiguousarray(descr, dtype=fdt)[None], row_scale=None if rs is None else rs[None]))
+        return tuple(out)
 
     def get_x0(self, optinit="zeros"):
         """functional.py:629-660"""

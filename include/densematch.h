@@ -285,6 +285,22 @@ int dm_fmap_fit_fused(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D,
 int dm_fmap_descr_ops(dm_ctx* ctx, int B, int N, int D, int k, const float* Phi, int ld, const float* mass,
                       const void* F, int f_dtype, double* ops);
 
+/* ops[b][p] (B, D, k, k) fp64: the orientation operator of descriptor p in the reduced basis of mesh b,
+ *   pinv diag(1 / area) W_p Phi,   W_p the sparse operator g -> <n x grad f_p, grad g> summed over the faces around a vertex
+ * (pyFM/mesh/geometry.py:919-985 get_orientation_op; one operand of FunctionalMapping.compute_orientation_op, pyFM/functional.py:686-728,
+ * and of orientation_op_torch inside energy_func_std, base_functions.py:430-478).  With left = Phi * row_scale[:, None]:
+ *   row_scale = mass / vertex_areas: compute_orientation_op's form;  row_scale = null (ones): energy_func_std's (area = diag(A) cancels).
+ * verts (B,N,3) fp64, faces (B,M,3) int32 with every index of a used face in [0, N) (the caller checks; the kernels clamp), n_faces
+ * (HOST, B; null: M each): faces beyond n_faces[b] are padding and contribute nothing.  F (B,N,D) fp16 | fp32 as staged for the fit.
+ * All descriptors of a mesh are ONE float64 matrix-core product (D k) x 3M times 3M x k, split-K into workspace partials added in a fixed
+ * order; the split follows from (D, k) alone: a mesh's operators are the same bits in every batch it is part of.  B <= 65535. */
+int dm_fmap_orient_ops(dm_ctx* ctx, int B, int N, int M, int D, int k, const double* verts, const int32_t* faces,
+                       const int32_t* n_faces, const float* Phi, int ld, const double* row_scale /*nullable*/,
+                       const void* F, int f_dtype, double* ops);
+int dm_fmap_orient_ops_f64(dm_ctx* ctx, int B, int N, int M, int D, int k, const double* verts, const int32_t* faces,
+                           const int32_t* n_faces, const double* Phi, int ld, const double* row_scale /*nullable*/,
+                           const void* F, int f_dtype, double* ops);
+
 /* ---- functional map -> vertex maps ---------------------------------------
  * With G = Phi2[:, :k2] C Phi1[:, :k1]^T (never materialised):
  *   knn21[i] = argmin_j |C Phi1_j|^2 - 2 G_ij      (pyFM/spectral/convert.py:138-140)
