@@ -65,6 +65,8 @@ SIGNATURES = {
     "dm_precise_map": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p]),
     "dm_linear_sum_assignment": (_i, [_p, _i, _i, _i, _p, _i, _p, _p]),
     "dm_lsa_gather": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p]),
+    "dm_map_metrics": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p]),
+    "dm_geodesic_diameter": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "dm_lsa_indicator_ok": (_i, [_p, _i, _i, _i, _i]),
     "dm_lsa_indicator": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _p]),
     "dm_p2p_to_fm_lstsq": (_i, [_p, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p]),

@@ -1274,6 +1274,232 @@ class MatchEngine:
             out[b][i, j] = out[b][j, i] = m
         return out[0] if single else out
 
+    # ------------------------------------------------------------- map quality measures on the geodesic matrices (dm_map_metrics)
+    MM_ACCURACY, MM_CONTINUITY, MM_COVERAGE = 0, 1, 2
+
+    @staticmethod
+    def _numpy_index(lst, n, who):
+        """an index list with NumPy's rules against an axis of length n: integers in [-n, n), negatives counted from the end
+        (IndexError otherwise, NumPy's text); returned as non-negative int32"""
+        import numpy as np
+        a = np.asarray(lst.cpu() if isinstance(lst, torch.Tensor) else lst)
+        if a.ndim != 1:
+            raise ValueError(f"{who}: an index list must be one-dimensional")
+        if a.size == 0:
+            return np.zeros(0, np.int32)
+        if not np.issubdtype(a.dtype, np.integer):
+            raise IndexError(f"{who}: arrays used as indices must be of integer type")
+        lo, hi = int(a.min()), int(a.max())
+        if lo < -n or hi >= n:
+            raise IndexError(f"{who}: index {lo if lo < -n else hi} is out of bounds for axis 0 with size {n}")
+        return np.where(a < 0, a + n, a).astype(np.int32)
+
+    def _mm_batch(self, P, B, N, mesh, n_verts, who):
+        """the mesh of every problem (P,) and the vertex counts (B,) of a call, checked"""
+        import numpy as np
+        mesh = np.zeros(P, np.int64) if mesh is None else np.broadcast_to(np.asarray(mesh, np.int64), (P,))
+        if P and (mesh.min() < 0 or mesh.max() >= B):
+            raise ValueError(f"{who}: mesh indices must lie in [0, {B})")
+        nv = np.full(B, N, np.int64) if n_verts is None else np.broadcast_to(np.asarray(n_verts, np.int64), (B,))
+        if nv.min() < 1 or nv.max() > N:
+            raise ValueError(f"{who}: n_verts must lie in [1, N]")
+        return mesh, np.ascontiguousarray(nv, np.int32)
+
+    class _IndexPool:
+        """the index array of one call: a list object that several problems pass is stored once"""
+
+        def __init__(self):
+            self.parts, self.off, self.seen = [], 0, {}
+
+        def add(self, obj, extra, make):
+            key = (id(obj),) + extra
+            if key not in self.seen:
+                a = make()
+                self.seen[key] = (self.off, a, obj)          # (obj is held: its id stays its own for the call)
+                self.parts.append(a)
+                self.off += a.size
+            return self.seen[key][:2]
+
+        def array(self):
+            import numpy as np
+            return np.concatenate(self.parts) if self.parts else np.zeros(0, np.int32)
+
+    def _map_metrics_run(self, D, D2, nv, nv2, area, idx, table, scale, n_all):
+        """ONE dm_map_metrics launch on a prepared index array and table (P, 8); the values (P,) and `all` (n_all,) as NumPy arrays.
+        D / D2: the tuples of _lsa_gather_D or None; area: (B, N) float64 device or None."""
+        import numpy as np
+        P = int(table.shape[0])
+        if P == 0:
+            return np.zeros(0, np.float64), np.zeros(0, np.float64)
+        if D is not None:
+            Dd, B, N, ld = D
+        else:
+            Dd, B, N, ld = None, int(area.shape[0]), int(area.shape[1]), int(area.shape[1])
+        D2d, B2, N2, ld2 = D2 if D2 is not None else (None, 0, 0, 0)
+        idx_d = torch.as_tensor(np.ascontiguousarray(idx, np.int32)).to(self.device) if len(idx) else torch.zeros(1, dtype=torch.int32, device=self.device)
+        table = np.ascontiguousarray(table, np.int32)
+        scale = None if scale is None else np.ascontiguousarray(scale, np.float64)
+        value = torch.empty((P,), dtype=torch.float64, device=self.device)
+        info = torch.empty((P,), dtype=torch.int32, device=self.device)
+        every = torch.empty((n_all,), dtype=torch.float64, device=self.device) if n_all else None
+        self._chk(self.lib.dm_map_metrics(self.ctx, B, N, ld, _ptr(Dd), B2, N2, ld2, _ptr(D2d), C.c_void_p(nv.ctypes.data),
+                                          C.c_void_p(nv2.ctypes.data) if nv2 is not None else C.c_void_p(0), _ptr(area),
+                                          int(len(idx)), _ptr(idx_d), P, C.c_void_p(table.ctypes.data),
+                                          C.c_void_p(scale.ctypes.data) if scale is not None else C.c_void_p(0), int(n_all),
+                                          _ptr(value), _ptr(every), _ptr(info)))
+        if int(info.max()) != 0:                             # (the lists were checked here: not reached through this class)
+            raise IndexError("map metrics: an index outside its mesh")
+        return value.cpu().numpy(), (every.cpu().numpy() if n_all else np.zeros(0, np.float64))
+
+    def map_metrics_table(self, idx, table, D=None, D2=None, area=None, scale=None, n_verts=None, n_verts2=None, n_all=0):
+        """dm_map_metrics as the header states it, for callers that build the table themselves (problems of all three kinds in one
+        launch): idx (n_idx,) int32 non-negative indices, table (P, 8) int32 rows (kind, mesh, mesh2, offset a, offset b, length,
+        aux, flags), scale (P,) or None; D / D2 as in lsa_gather, area (B, N).  Returns (values (P,), all (n_all,)) as NumPy arrays;
+        ValueError for a table the library refuses, IndexError for an index outside its mesh."""
+        import numpy as np
+        Dt = None if D is None else self._lsa_gather_D(D, "map_metrics_table")
+        D2t = None if D2 is None else self._lsa_gather_D(D2, "map_metrics_table")
+        if area is not None:
+            area = self._dev(area if isinstance(area, torch.Tensor) else torch.as_tensor(np.asarray(area, np.float64)), torch.float64, "area")
+            area = area[None] if area.dim() == 1 else area
+        if Dt is None and area is None:
+            raise ValueError("map_metrics_table: D or area is needed")
+        if Dt is not None and area is not None and tuple(area.shape) != (Dt[1], Dt[2]):
+            raise ValueError("map_metrics_table: area must be (B, N) like D")
+        B, N = (Dt[1], Dt[2]) if Dt is not None else (int(area.shape[0]), int(area.shape[1]))
+        _, nv = self._mm_batch(0, B, N, None, n_verts, "map_metrics_table")
+        nv2 = None if (D2t is None or n_verts2 is None) else self._mm_batch(0, D2t[1], D2t[2], None, n_verts2, "map_metrics_table")[1]
+        table = np.asarray(table, np.int32).reshape(-1, 8)
+        return self._map_metrics_run(Dt, D2t, nv, nv2, area, np.asarray(idx, np.int32).reshape(-1), table, scale, int(n_all))
+
+    def geodesic_diameter(self, D, n_verts=None):
+        """np.max(D[b, :n_verts[b], :n_verts[b]]) of every mesh of a padded batch (dm_geodesic_diameter; the diameter that the
+        reference's geodesic_label_errors normalises by, diffusion_net/geometry.py:773): (B,) float64 NumPy, NaN where an entry is
+        NaN.  D: (N, N) or (B, N, N), NumPy or torch; a float64 device tensor is read in place."""
+        import numpy as np
+        Dd, B, N, ld = self._lsa_gather_D(D, "geodesic_diameter")
+        _, nv = self._mm_batch(0, B, N, None, n_verts, "geodesic_diameter")
+        out = torch.empty((B,), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.dm_geodesic_diameter(self.ctx, B, N, ld, _ptr(Dd), C.c_void_p(nv.ctypes.data), _ptr(out)))
+        return out.cpu().numpy()
+
+    def map_accuracy(self, D, p2p_list, gt_list, mesh=None, scale=None, return_all=False, n_verts=None):
+        """The reference's accuracy (pyFM/eval/evaluate.py:29-36) for P maps in ONE device call: problem p is
+        d = D[mesh[p]][(p2p_list[p], gt_list[p])] -- the row from the map, the column from the ground truth --, d /= scale[p] element
+        by element where a scale is given, and d.mean().  D as in lsa_gather (a float64 device tensor is read in place); index lists
+        with NumPy's rules (-n <= i < n, IndexError otherwise); a list object passed for several problems is uploaded once.
+        scale: None, one number, one number per problem, or "diameter" (geodesic_diameter, once for the batch).  An empty list gives
+        NumPy's nan without a launch.  Returns the means (P,) float64 NumPy; with return_all=True also the list of the d arrays."""
+        import numpy as np
+        Dt = self._lsa_gather_D(D, "map_accuracy")
+        B, N = Dt[1], Dt[2]
+        p2p_list, gt_list = list(p2p_list), list(gt_list)
+        P = len(p2p_list)
+        if len(gt_list) != P:
+            raise ValueError("map_accuracy: as many ground-truth lists as maps")
+        mesh, nv = self._mm_batch(P, B, N, mesh, n_verts, "map_accuracy")
+        if isinstance(scale, str):
+            if scale != "diameter":
+                raise ValueError("map_accuracy: scale must be None, numbers or 'diameter'")
+            sc = self.geodesic_diameter(Dt[0], nv)[mesh]
+        elif scale is not None:
+            sc = np.array(np.broadcast_to(np.asarray(scale, np.float64), (P,)))
+        else:
+            sc = None
+        pool, rows, where, n_all = self._IndexPool(), [], [], 0
+        values = np.full(P, np.nan)
+        for p in range(P):
+            n = int(nv[mesh[p]])
+            oa, a = pool.add(p2p_list[p], (n,), lambda: self._numpy_index(p2p_list[p], n, "map_accuracy"))
+            ob, b = pool.add(gt_list[p], (n,), lambda: self._numpy_index(gt_list[p], n, "map_accuracy"))
+            if a.size != b.size:
+                raise ValueError(f"map_accuracy: problem {p}: a map of {a.size} and a ground truth of {b.size} entries")
+            if a.size == 0:
+                values[p] = np.zeros(0).mean()               # (NumPy's nan and its warning)
+                continue
+            flags = (1 if sc is not None else 0) | (2 if return_all else 0)
+            rows.append((self.MM_ACCURACY, mesh[p], 0, oa, ob, a.size, n_all, flags))
+            where.append(p)
+            n_all += a.size if return_all else 0
+        table = np.asarray(rows, np.int32).reshape(-1, 8)
+        where = np.asarray(where, np.int64)
+        got, every = self._map_metrics_run(Dt, None, nv, None, None, pool.array(), table, None if sc is None else sc[where], n_all)
+        values[where] = got
+        if not return_all:
+            return values
+        dists = [np.zeros(0) for _ in range(P)]
+        for row, p in zip(table, where):
+            dists[p] = every[row[6]:row[6] + row[5]].copy()
+        return values, dists
+
+    def map_continuity(self, D1, D2, p2p_list, edges_list, mesh1=None, mesh2=None, n_verts1=None, n_verts2=None):
+        """The reference's continuity (pyFM/eval/evaluate.py:63-66) for P maps in ONE device call: problem p is
+        np.mean(D1[mesh1[p]][(p2p[e0], p2p[e1])] / D2[mesh2[p]][(e0, e1)]) over the edges (e0, e1) = edges_list[p] (E, 2) of the
+        target mesh, p2p = p2p_list[p] its map into the source mesh.  D2=None: both sides are meshes of D1.  IEEE division without
+        guards: an edge of length zero gives inf or nan and the mean carries it, as NumPy's does.  Index rules, sharing of list
+        objects, empty lists and the return as in map_accuracy."""
+        import numpy as np
+        D1t = self._lsa_gather_D(D1, "map_continuity")
+        D2t = D1t if D2 is None else self._lsa_gather_D(D2, "map_continuity")
+        p2p_list, edges_list = list(p2p_list), list(edges_list)
+        P = len(p2p_list)
+        if len(edges_list) != P:
+            raise ValueError("map_continuity: as many edge lists as maps")
+        mesh1, nv1 = self._mm_batch(P, D1t[1], D1t[2], mesh1, n_verts1, "map_continuity")
+        mesh2, nv2 = self._mm_batch(P, D2t[1], D2t[2], mesh2, n_verts1 if (D2 is None and n_verts2 is None) else n_verts2, "map_continuity")
+        pool, rows, where = self._IndexPool(), [], []
+        values = np.full(P, np.nan)
+
+        def edge_lists(edges, n_map, n2):
+            e = np.asarray(edges.cpu() if isinstance(edges, torch.Tensor) else edges)
+            if e.ndim != 2 or e.shape[1] != 2:
+                raise ValueError("map_continuity: edges must be (E, 2)")
+            flat = e.T.reshape(-1)                           # every e0, then every e1
+            in_map = self._numpy_index(flat, n_map, "map_continuity")
+            if n_map != n2 and not np.array_equal(in_map, self._numpy_index(flat, n2, "map_continuity")):
+                raise ValueError("map_continuity: negative edge indices need a map with one entry per target vertex")
+            return in_map
+
+        for p in range(P):
+            n1, n2 = int(nv1[mesh1[p]]), int(nv2[mesh2[p]])
+            oa, a = pool.add(p2p_list[p], (n1,), lambda: self._numpy_index(p2p_list[p], n1, "map_continuity"))
+            if a.size == 0 and np.size(edges_list[p]):
+                raise IndexError("map_continuity: index 0 is out of bounds for axis 0 with size 0")
+            ob, e = pool.add(edges_list[p], (a.size, n2), lambda: edge_lists(edges_list[p], a.size, n2))
+            if e.size == 0:
+                values[p] = np.zeros(0).mean()
+                continue
+            rows.append((self.MM_CONTINUITY, mesh1[p], mesh2[p], oa, ob, e.size // 2, a.size, 0))
+            where.append(p)
+        table = np.asarray(rows, np.int32).reshape(-1, 8)
+        got, _ = self._map_metrics_run(D1t, D2t, nv1, nv2, None, pool.array(), table, None, 0)
+        values[np.asarray(where, np.int64)] = got
+        return values
+
+    def map_coverage(self, area, p2p_list, mesh=None, n_verts=None):
+        """The reference's coverage (pyFM/eval/evaluate.py:89-91) for P maps in ONE device call: problem p is
+        area[mesh[p]][np.unique(p2p_list[p])].sum() / area[mesh[p]][:n].sum().  area: (N,) or (B, N) vertex areas, NumPy or torch.
+        Index rules, sharing of list objects and the return as in map_accuracy; an empty map covers nothing (0.0, as NumPy gives)."""
+        import numpy as np
+        if not isinstance(area, torch.Tensor):
+            area = torch.as_tensor(np.asarray(area, np.float64))
+        if area.dim() == 1:
+            area = area[None]
+        if area.dim() != 2 or area.shape[1] < 1:
+            raise ValueError("map_coverage: area must be (N,) or (B, N)")
+        area = self._dev(area, torch.float64, "area")
+        B, N = int(area.shape[0]), int(area.shape[1])
+        p2p_list = list(p2p_list)
+        P = len(p2p_list)
+        mesh, nv = self._mm_batch(P, B, N, mesh, n_verts, "map_coverage")
+        pool, rows = self._IndexPool(), []
+        for p in range(P):
+            n = int(nv[mesh[p]])
+            oa, a = pool.add(p2p_list[p], (n,), lambda: self._numpy_index(p2p_list[p], n, "map_coverage"))
+            rows.append((self.MM_COVERAGE, mesh[p], 0, oa, 0, a.size, 0, 0))
+        table = np.asarray(rows, np.int32).reshape(-1, 8)
+        return self._map_metrics_run(None, None, nv, None, area, pool.array(), table, None, 0)[0]
+
     def lsa_indicator_ok(self, N1, N2, k1, k2):
         return bool(self.lib.dm_lsa_indicator_ok(self.ctx, int(N1), int(N2), int(k1), int(k2)))
 

@@ -501,6 +501,40 @@ int dm_lsa_gather(dm_ctx* ctx, int B, int N, int ld, const double* D, int n_idx,
                   const int32_t* problems /* host, P*6 */, int maximize, int32_t* col_of_row /*nullable*/, double* mean /* P */,
                   int32_t* info /* P */);
 
+/* ---- map quality measures on the geodesic matrices --------------------------------------
+ * Replaces the host fancy-indexing of pyFM/eval/evaluate.py: accuracy (:29-36), continuity (:63-66), coverage (:89-91), for P
+ * problems on the matrices of a padded batch in ONE launch, and np.max of a distance matrix (the geodesic diameter that
+ * diffusion_net/geometry.py:773 normalises by).  No N x N matrix crosses to the host.
+ *   dm_map_metrics  D (B,N,ld) fp64 device, read in place (ld >= N: a view with a row stride is accepted, as dm_lsa_gather does;
+ *     nullable when every problem is a coverage); D2 (B2,N2,ld2) nullable = D (the matrices that a continuity's edges index);
+ *     n_verts (B) / n_verts2 (B2) HOST, nullable = N / N2: the vertex counts of a padded batch; area (B,N) fp64 device, nullable
+ *     (the vertex areas of a coverage); idx (n_idx) int32 device: every index list of the call once, lists may be shared between
+ *     problems; table (P,8) int32 HOST (the library sorts it by length, longest first, and uploads it), a row being
+ *         kind, mesh, mesh2, offset a, offset b, length, aux, flags
+ *       kind 0 accuracy:   d[i] = D[mesh][idx[a + i]][idx[b + i]], i < length -- the row from the map, the column from the ground
+ *                          truth -- d[i] /= scale[p] element by element when flags & 1, value = sum(d) / length; when flags & 2 the
+ *                          d[i] are also written to all[aux + i] (the reference's return_all)
+ *       kind 1 continuity: the map is idx[a : a + aux], the edges are (idx[b + e], idx[b + length + e]), e < length;
+ *                          value = mean_e( D[mesh][map[e0]][map[e1]] / D2[mesh2][e0][e1] ), IEEE division with no guards (a zero
+ *                          length gives inf or NaN and the mean carries it, as NumPy's does)
+ *       kind 2 coverage:   value = sum of area[mesh][v] over the DISTINCT values v of idx[a : a + length], divided by the sum of
+ *                          area[mesh][:n_verts[mesh]]; length 0 is legal (0 / total)
+ *     scale (P) fp64 HOST, nullable; n_all = the elements of `all`.  Outputs (device): value (P), all (nullable), info (P): 0, or 1
+ *     where an index lies outside [0, n_verts) of its mesh (value NaN; such an index is never used as an address; the caller
+ *     checks its lists, as for dm_lsa_gather).
+ *     One workgroup per problem; a sum is taken in an order fixed by the problem alone (256 strided partial sums in ascending
+ *     order, then a binary tree), the coverage sums in ascending vertex order (np.unique's): a problem's bits do not depend on
+ *     what shares the call, on B, on the padding or on ld.  No floating-point atomics.  N, N2 <= 16384.  P = 0 is legal.
+ *     DM_EINVAL for a kind, mesh, offset or length outside its range and for a coverage without `area`.  The call synchronises
+ *     the stream once (the table's upload).
+ *   dm_geodesic_diameter  out[b] = np.max(D[b, :n, :n]), n = n_verts[b] (HOST, nullable = N): NaN if any entry is NaN (np.max's
+ *     rule); rows / columns past n and the columns N..ld are never read.  A two-stage max reduction. */
+int dm_map_metrics(dm_ctx* ctx, int B, int N, int ld, const double* D, int B2, int N2, int ld2, const double* D2 /*nullable*/,
+                   const int32_t* n_verts /*host, nullable*/, const int32_t* n_verts2 /*host, nullable*/, const double* area /*nullable*/,
+                   int n_idx, const int32_t* idx, int P, const int32_t* table /* host, P*8 */, const double* scale /*host, nullable*/,
+                   int n_all, double* value /* P */, double* all /*nullable*/, int32_t* info /* P */);
+int dm_geodesic_diameter(dm_ctx* ctx, int B, int N, int ld, const double* D, const int32_t* n_verts /*host, nullable*/, double* out /* B */);
+
 /* ---- vertex map -> functional map, least squares -------------------------------
  * C[b] = argmin_X |Phi2[b][:, :k2] X - Phi1[b][p21[b], :k1]|_F   (k2 x k1) fp64, no mass matrix.
  * Replaces pyFM/spectral/convert.py:51 (p2p_to_FM with A2 = None: scipy.linalg.lstsq), the form ICP and ZoomOut on
