@@ -77,6 +77,11 @@ SIGNATURES = {
     "dm_fps_heat": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dm_graph_geodesic": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "dm_fps_graph": (_i, [_p, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
+    "dm_eigh_smallest": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "dm_fmn_orth_defect": (_i, [_p, _i, _i, _p, _i, _p]),
+    "dm_fmn_cycle_costs": (_i, [_p, _i, _i, _p, _i, _i, _p, _p]),
+    "dm_fmn_quad_form": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "dm_fmn_cclb": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "dm_spectral_signatures": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
 }
 

@@ -100,6 +100,7 @@ extern "C" int dm_set_option(dm_ctx* ctx, const char* name, int value) {
     else if (n == "zoomout_sub_fused") ctx->opt_zoomout_sub_fused = value;
     else if (n == "fps_heat_route") ctx->opt_fps_heat_route = value;
     else if (n == "graph_geod_device") ctx->opt_graph_geod_device = value;
+    else if (n == "fmn_eig_route") ctx->opt_fmn_eig_route = value;
     else if (n == "proj_onepass") ctx->opt_proj_onepass = value;
     else if (n == "energy_keep_gram") { ctx->opt_energy_keep_gram = value; ctx->gram_valid = false; }
     else return dm_fail(ctx, DM_EINVAL, "dm_set_option: unknown option '%s'", name);

@@ -182,6 +182,38 @@ __global__ __launch_bounds__(256) void gershgorin_kernel(const double* __restric
     if (t == 0) lmax[b] = sh[0];
 }
 
+// ---- dense symmetric operator (dm_eigh_smallest) ------------------------------------------------------------------------------
+// The same recurrence as spmm_ell_kernel's as the epilogue of a gemm_nt_f64 tile: Ynew = alpha (A Y - cc Y) - beta Yprev with
+// (alpha, cc, beta) = coef[b][step] or (1, 0, 0); the product's sum runs in the tile's fixed k order.
+struct EigOutCheb {
+    const double* y; const double* yprev; double* ynew; long long stride_b; int ld; const double* coef; int step;
+    __device__ __forceinline__ void store(int b, int i, int j, double v) const {
+        const long long o = b * stride_b + (long long)i * ld + j;
+        double alpha = 1.0, cc = 0.0, beta = 0.0;
+        if (coef) { const double* k = coef + ((long long)b * EIG_MAX_DEG + step) * 3; alpha = k[0]; cc = k[1]; beta = k[2]; }
+        double out = alpha * (v - cc * y[o]);
+        if (yprev && beta != 0.0) out -= beta * yprev[o];
+        ynew[o] = out;
+    }
+};
+// lmax[b] = max_j sum_i |A[i][j]|: the Gershgorin bound of a dense SYMMETRIC matrix (column sums = row sums; thread j walks
+// column j, so a wave reads whole rows), rows added in index order
+__global__ __launch_bounds__(256) void gershgorin_dense_kernel(const double* __restrict__ A, int n, int lda, double* __restrict__ lmax) {
+    __shared__ double sh[256];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const double* Ab = A + (long long)b * n * lda;
+    double mx = 0.0;
+    for (int j = t; j < n; j += 256) {
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) s += fabs(Ab[(long long)i * lda + j]);
+        mx = fmax(mx, s);
+    }
+    sh[t] = mx;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) { if (t < off) sh[t] = fmax(sh[t], sh[t + off]); __syncthreads(); }
+    if (t == 0) lmax[b] = sh[0];
+}
+
 // coefficients of the scaled Chebyshev recurrence of degree `deg` damping [theta[m-1], lmax], normalised at theta[0]
 // (Y_1 = (sigma_1 / e)(L - c) X;  Y_{j+1} = (2 sigma_{j+1} / e)(L - c) Y_j - sigma_j sigma_{j+1} Y_{j-1})
 __global__ void cheb_coef_kernel(const double* __restrict__ theta, int m, const double* __restrict__ lmax, int deg, double* __restrict__ coef) {
@@ -436,6 +468,8 @@ __global__ __launch_bounds__(256) void ritz_sort_kernel(const double* __restrict
 
 // Phi[b][i][c] = X[b][i][c] / sqrt(mass[b][i]) for c < k, sign fixed so that the entry of largest magnitude is positive;
 // lam[b][c] = theta[b][c]
+// (SCALED = false, the dense symmetric operator of dm_eigh_smallest: no mass, Phi = the signed Ritz vectors themselves)
+template <bool SCALED>
 __global__ __launch_bounds__(256) void eig_finish_kernel(const double* __restrict__ X, int N, int m, int k, const float* __restrict__ mass,
                                                          const double* __restrict__ theta, double* __restrict__ Phi, double* __restrict__ lam) {
     __shared__ double sh[256];
@@ -453,8 +487,10 @@ __global__ __launch_bounds__(256) void eig_finish_kernel(const double* __restric
         __syncthreads();
     }
     const double sgn = X[((long long)b * N + shi[0]) * m + c] < 0.0 ? -1.0 : 1.0;
-    for (int i = t; i < N; i += 256)
-        Phi[((long long)b * N + i) * k + c] = sgn * X[((long long)b * N + i) * m + c] / sqrt((double)mass[(long long)b * N + i]);
+    for (int i = t; i < N; i += 256) {
+        if constexpr (SCALED) Phi[((long long)b * N + i) * k + c] = sgn * X[((long long)b * N + i) * m + c] / sqrt((double)mass[(long long)b * N + i]);
+        else Phi[((long long)b * N + i) * k + c] = sgn * X[((long long)b * N + i) * m + c];
+    }
     if (t == 0) lam[(long long)b * k + c] = theta[(long long)b * m + c];
 }
 
@@ -610,6 +646,15 @@ static int launch_unit_columns(dm_ctx* ctx, double* X, int B, int N, int m, doub
     return DM_OK;
 }
 
+// The operator of an iteration: the ELL rows of A^-1/2 W A^-1/2 with the lumped masses (dm_eigenbasis), or a dense symmetric matrix
+// (dm_eigh_smallest: dA set, no mass scaling).  Everything but the operator product, the Gershgorin bound and the final scaling is shared.
+struct eig_op {
+    const int32_t* ell_cols = nullptr; const double* ell_vals = nullptr; int nnz = 0; const float* mass = nullptr;
+    const double* dA = nullptr; int lda = 0;
+};
+static int eig_core(dm_ctx* ctx, int B, int N, const eig_op& op, int k, int guard, int n_iter, int degree, int warm_start, double* X,
+                    double* lam, double* Phi, double* resid);
+
 extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* ell_cols, const double* ell_vals, const float* mass,
                              int k, int guard, int n_iter, int degree, int warm_start, double* X /* B*N*(k+guard), in/out */,
                              double* lam /* B*k */, double* Phi /* B*N*k */, double* resid /* B */) {
@@ -626,6 +671,34 @@ extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* 
     //  at N = 2048 -- slow, but a mesh whose wanted range passes the middle of its spectrum is solved like the reference's ARPACK solves it)
     DM_REQUIRE(ctx, m <= N && m <= (dense ? 2048 : 512), "k + guard must be <= min(N, 512) (dense route: N <= 2048)");
     DM_REQUIRE(ctx, degree >= 2 && degree <= EIG_MAX_DEG, "filter degree must be in [2, 64]");
+    eig_op op;
+    op.ell_cols = ell_cols; op.ell_vals = ell_vals; op.nnz = nnz; op.mass = mass;
+    return eig_core(ctx, B, N, op, k, guard, n_iter, degree, warm_start, X, lam, Phi, resid);
+}
+
+// The k smallest eigenpairs of B dense symmetric n x n matrices (the quadratic form of a functional map network, dm_fmn.hip): the
+// iteration of dm_eigenbasis on a dense operator, without mass scaling.  warm_start = 2: X = the identity, k + guard = n <= 512, one
+// Rayleigh-Ritz step = the Jacobi eigendecomposition of A itself.
+extern "C" int dm_eigh_smallest(dm_ctx* ctx, int B, int n, const double* A, int lda, int k, int guard, int n_iter, int degree, int warm_start,
+                                double* X /* B*n*(k+guard), in/out */, double* lam /* B*k */, double* V /* B*n*k */, double* resid /* B */) {
+    if (!ctx) return DM_EINVAL;
+    const bool full = warm_start == 2;
+    if (full) n_iter = 0;
+    DM_REQUIRE(ctx, B > 0 && n > 0 && k > 0 && guard >= 0 && (n_iter > 0 || full), "sizes must be positive");
+    DM_REQUIRE(ctx, warm_start >= 0 && warm_start <= 2, "warm_start must be 0, 1 or 2");
+    DM_REQUIRE(ctx, n <= 4096 && lda >= n, "n must be <= 4096 and lda >= n");
+    DM_REQUIRE(ctx, k + guard <= n && k + guard <= 512, "k + guard must be <= min(n, 512)");
+    DM_REQUIRE(ctx, !full || k + guard == n, "warm_start = 2 takes the whole space: k + guard = n <= 512");
+    DM_REQUIRE(ctx, A && X && lam && V && resid, "null pointer");
+    DM_REQUIRE(ctx, degree >= 2 && degree <= EIG_MAX_DEG, "filter degree must be in [2, 64]");
+    eig_op op;
+    op.dA = A; op.lda = lda;
+    return eig_core(ctx, B, n, op, k, guard, n_iter, degree, warm_start, X, lam, V, resid);
+}
+
+static int eig_core(dm_ctx* ctx, int B, int N, const eig_op& op, int k, int guard, int n_iter, int degree, int warm_start, double* X,
+                    double* lam, double* Phi, double* resid) {
+    const int m = k + guard;
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bX = (size_t)B * N * m * 8, bM = (size_t)B * m * m * 8;
     eig_ws w;
@@ -654,7 +727,8 @@ extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* 
     DM_CHECK_HIP(ctx, hipMemsetAsync(w.fail, 0, (size_t)B * 4, ctx->stream));
     if (!Ya || !Yb || !Yc || !H || !V || !Q || !w.T || !w.W || !w.part || !theta || !coef || !lmax || !rbits)
         return dm_fail(ctx, DM_ENOMEM, "eigenbasis: workspace not reserved");
-    DM_LAUNCH(ctx, "eig_gershgorin", gershgorin_kernel, dim3(B), dim3(256), 0, ell_vals, N, nnz, lmax);
+    if (op.dA) DM_LAUNCH(ctx, "eig_gershgorin_dense", gershgorin_dense_kernel, dim3(B), dim3(256), 0, op.dA, N, op.lda, lmax);
+    else DM_LAUNCH(ctx, "eig_gershgorin", gershgorin_kernel, dim3(B), dim3(256), 0, op.ell_vals, N, op.nnz, lmax);
     int spmm_cw = 16;
     while (spmm_cw < m && spmm_cw < 256) spmm_cw <<= 1;
     // (a batch of sixteen meshes or more: the XCD-aware one-dimensional order, see the kernel; fewer would leave XCDs idle)
@@ -668,8 +742,16 @@ extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* 
     const int nbx4 = dm_cdiv(N, 256 / spmm_tpr);
     const dim3 gsp4 = spmm_xcd ? dim3((unsigned)(nbx4 * dm_cdiv(B, 8) * 8)) : dim3(nbx4, 1, B);
     auto launch_spmm = [&](const double* yin, const double* yprev, double* ynew, const double* cf, int step) -> int {
-        if (spmm4) DM_LAUNCH(ctx, "eig_spmm", spmm_ell4_kernel, gsp4, dim3(256), 0, ell_vals, ell_cols, N, nnz, yin, yprev, ynew, m, cf, step, spmm_tpr, spmm_xcd);
-        else DM_LAUNCH(ctx, "eig_spmm", spmm_ell_kernel, gsp, dim3(256), 0, ell_vals, ell_cols, N, nnz, yin, yprev, ynew, m, cf, step, spmm_cw, spmm_xcd);
+        if (op.dA) {            // ynew[i][c] = sum_j A[i][j] yin[j][c]: rows of A against the columns of the block, read transposed
+            KRowsF64 ar{op.dA, (long long)N * op.lda, op.lda, N, N, 0};
+            KRowsF64 yc{yin, (long long)N * m, m, m, N, 1};
+            EigOutCheb out{yin, yprev, ynew, (long long)N * m, m, cf, step};
+            DM_LAUNCH(ctx, "eig_dense_mm", (gemm_nt_f64<KRowsF64, KRowsF64, EigOutCheb>), dim3(dm_cdiv(N, NT_T) * dm_cdiv(m, NT_T), 1, B), dim3(256), 0,
+                      ar, yc, out, N, m, N);
+            return DM_OK;
+        }
+        if (spmm4) DM_LAUNCH(ctx, "eig_spmm", spmm_ell4_kernel, gsp4, dim3(256), 0, op.ell_vals, op.ell_cols, N, op.nnz, yin, yprev, ynew, m, cf, step, spmm_tpr, spmm_xcd);
+        else DM_LAUNCH(ctx, "eig_spmm", spmm_ell_kernel, gsp, dim3(256), 0, op.ell_vals, op.ell_cols, N, op.nnz, yin, yprev, ynew, m, cf, step, spmm_cw, spmm_xcd);
         return DM_OK;
     };
     const double* Xcur = X;
@@ -689,16 +771,8 @@ extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* 
         if (rc) return rc;
         rc = eig_gram(ctx, w, Xcur, Ya, H, 1);
         if (rc) return rc;
-        const size_t jac_lds = (size_t)2 * m * m * 8;
-        if (jac_lds <= 128 * 1024) {
-            int rc_ = dm_grant_lds(ctx, (const void*)jacobi_eigh_kernel<true>, jac_lds);
-            if (rc_) return rc_;
-            DM_LAUNCH(ctx, "eig_jacobi", jacobi_eigh_kernel<true>, dim3(B), dim3(1024), jac_lds, H, V, m, 30);
-        } else {
-            DM_LAUNCH(ctx, "eig_jacobi", jacobi_eigh_kernel<false>, dim3(B), dim3(1024), 0, H, V, m, 30);
-        }
-        DM_LAUNCH(ctx, "eig_ritz_sort", ritz_sort_kernel, dim3(B), dim3(256), (size_t)m * 8 + (size_t)m * 4, (const double*)H, (const double*)V, m,
-                  theta, Q);
+        rc = dm_eig_jacobi_sorted(ctx, B, m, H, V, theta, Q);
+        if (rc) return rc;
         rc = eig_apply(ctx, w, Xcur, Q, 1, 0.0, 1.0, Yb);                            // Ritz vectors: (X Q)_ic = sum_k X_ik Q_kc
         if (rc) return rc;
         DM_CHECK_HIP(ctx, hipMemcpyAsync(X, Yb, bX, hipMemcpyDeviceToDevice, ctx->stream));
@@ -734,6 +808,22 @@ extern "C" int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* 
     DM_LAUNCH(ctx, "eig_residual", ritz_residual_kernel, dim3(k, B), dim3(256), 0, (const double*)X, (const double*)Ya, N, m, (const double*)theta, rbits);
     DM_CHECK_HIP(ctx, hipMemcpyAsync(resid, rbits, (size_t)B * 8, hipMemcpyDeviceToDevice, ctx->stream));
     DM_LAUNCH(ctx, "eig_fail", eig_fail_kernel, dim3(dm_cdiv(B, 256)), dim3(256), 0, (const int*)w.fail, B, resid);
-    DM_LAUNCH(ctx, "eig_finish", eig_finish_kernel, dim3(k, B), dim3(256), 0, (const double*)X, N, m, k, mass, (const double*)theta, Phi, lam);
+    if (op.dA) DM_LAUNCH(ctx, "eig_finish", eig_finish_kernel<false>, dim3(k, B), dim3(256), 0, (const double*)X, N, m, k, op.mass, (const double*)theta, Phi, lam);
+    else DM_LAUNCH(ctx, "eig_finish", eig_finish_kernel<true>, dim3(k, B), dim3(256), 0, (const double*)X, N, m, k, op.mass, (const double*)theta, Phi, lam);
+    return DM_OK;
+}
+
+// Eigendecomposition of B symmetric m x m matrices (dm_internal.h): the Rayleigh-Ritz step's Jacobi solve and sort on their own.
+// H is overwritten, V is scratch; theta (B, m) ascending, Q (B, m, m) with the eigenvectors as columns.
+int dm_eig_jacobi_sorted(dm_ctx* ctx, int B, int m, double* H, double* V, double* theta, double* Q) {
+    const size_t jac_lds = (size_t)2 * m * m * 8;
+    if (jac_lds <= 128 * 1024) {
+        int rc = dm_grant_lds(ctx, (const void*)jacobi_eigh_kernel<true>, jac_lds);
+        if (rc) return rc;
+        DM_LAUNCH(ctx, "eig_jacobi", jacobi_eigh_kernel<true>, dim3(B), dim3(1024), jac_lds, H, V, m, 30);
+    } else {
+        DM_LAUNCH(ctx, "eig_jacobi", jacobi_eigh_kernel<false>, dim3(B), dim3(1024), 0, H, V, m, 30);
+    }
+    DM_LAUNCH(ctx, "eig_ritz_sort", ritz_sort_kernel, dim3(B), dim3(256), (size_t)m * 8 + (size_t)m * 4, (const double*)H, (const double*)V, m, theta, Q);
     return DM_OK;
 }

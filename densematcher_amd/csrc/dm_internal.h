@@ -62,6 +62,8 @@ struct dm_ctx {
     int opt_fps_heat_route = 0;  // dm_fps_heat: 0 = the all-pairs rows when their work space fits, else one solve per sample; 1 / 2 force a route
     int opt_graph_geod_device = 1;   // the Python layer's choice for shortest paths along mesh edges (the default extract_fps, get_geodesic(dijkstra=True)):
                                  // 1 = dm_fps_graph / dm_graph_geodesic, 0 = SciPy's Dijkstra on the host; the same bits; the library only keeps the value
+    int opt_fmn_eig_route = 0;   // the Python layer's choice for the eigenproblem of a functional map network (MatchEngine.eigh_smallest): 0 by the sizes,
+                                 // 1 the full Jacobi eigendecomposition, 2 the filtered iteration; the library only keeps the value
     int opt_energy_keep_gram = 0;  // 1: dm_fmap_energy_grad keeps P = A A^T, Q = B A^T of its FIRST call and reuses them while A, B
                                    // (pointers and sizes) stay the same: the caller promises not to change their contents (the L-BFGS
                                    // driver: the projected descriptors are fixed during a fit).  Setting the option again drops them.
@@ -344,6 +346,10 @@ __device__ __forceinline__ void dm_c00_body(const dm_c00_args<TR>& z, int b, int
     }
 }
 #endif
+
+// eigendecomposition of B symmetric m x m matrices by the Jacobi kernel of dm_eigen.hip (H overwritten, V scratch (B, m, m)):
+// theta (B, m) ascending, Q (B, m, m) eigenvectors as columns
+int dm_eig_jacobi_sorted(dm_ctx* ctx, int B, int m, double* H, double* V, double* theta, double* Q);
 
 // linear assignment of B dense nr x nc matrices (dm_assign.hip), for callers that gather their matrices themselves (dm_lsa_gather.hip):
 // the caller reserves lsa_ws_bytes(B, nr, nc) of the arena and zeroes info (B); the argument lists are those of lsa_run's definition

@@ -132,7 +132,7 @@ class MatchEngine:
 
     OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0, "energy_keep_gram": 0,
                        "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
-                       "zoomout_sub_fused": 1, "fps_heat_route": 0, "graph_geod_device": 1}
+                       "zoomout_sub_fused": 1, "fps_heat_route": 0, "graph_geod_device": 1, "fmn_eig_route": 0}
 
     def set_option(self, name, value):
         """Choose between code paths of the library (include/densematch.h: dm_set_option).  Most settings return the same
@@ -143,7 +143,8 @@ class MatchEngine:
         between the one-factor device loop of subsampled ZoomOut (1) and the host-chained least-squares steps (0): the maps agree
         to 1e-9, not bit for bit; "graph_geod_device" chooses between the device kernels (1) and SciPy's Dijkstra on the host (0) for
         shortest paths along mesh edges (the default extract_fps / extract_fps_many, get_geodesic(dijkstra=True)): the two settings
-        agree bit for bit."""
+        agree bit for bit; "fmn_eig_route" chooses the route of eigh_smallest (0 by the sizes, 1 the full Jacobi eigendecomposition, 2 the
+        filtered iteration): eigenvalues and invariant subspaces agree to the residual, not bit for bit."""
         self._chk(self.lib.dm_set_option(self.ctx, name.encode(), int(value)))
         self._options[name] = int(value)
 
@@ -1081,6 +1082,144 @@ class MatchEngine:
             if bool(done.all()):
                 break
         return lam, Phi, resid, rounds
+
+    # ------------------------------------------------------------------ functional map networks (pyFM/FMN)
+    FMN_MAX_DIM, FMN_MAX_M = 4096, 256
+
+    def eigh_smallest(self, A, k, guard=None, tol=1e-9, max_rounds=12, degree=30):
+        """k smallest eigenpairs of dense symmetric matrices A (n, n) or (B, n, n), n <= 4096 (dm_eigh_smallest; the functional map
+        network's scipy.sparse.linalg.eigsh(W, k, sigma=-1e-6)).  Iterates as eigenbasis does, until max_j |A x_j - lam_j x_j| <= tol * d
+        with d = max_i |A_ii| -- for a symmetric matrix d <= max |lambda|, so the test is at least as strict as tol * lambda_max -- and
+        raises DenseMatchError when max_rounds pass without that.  Route ("fmn_eig_route" 0): the full Jacobi eigendecomposition (n <= 512,
+        one call) where n <= 128 or the filtered iteration has no room (2 (k + guard) > n), else the Chebyshev-filtered iteration; 1 / 2
+        force one.  Either route reads the residual back: one synchronisation per call on the Jacobi route, one per round on the filtered.
+        The start block of the filtered route is drawn from a fixed seed.
+        Returns (lam (B,k), V (B,n,k) orthonormal columns, largest entry of each positive, resid (B,), rounds); B dropped for a 2-D A."""
+        A = self._dev(A, torch.float64, "A")
+        single = A.dim() == 2
+        if single:
+            A = A[None]
+        if A.dim() != 3 or A.shape[1] != A.shape[2]:
+            raise ValueError("eigh_smallest: A must be (n, n) or (B, n, n)")
+        B, n, _ = A.shape
+        k = int(k)
+        if not 0 < k <= n:
+            raise ValueError(f"eigh_smallest: {k} eigenpairs asked of a {n} x {n} matrix")
+        if n > self.FMN_MAX_DIM:
+            raise ValueError(f"eigh_smallest: n = {n} is above the limit of {self.FMN_MAX_DIM}")
+        if guard is None:
+            guard = next((g for g in range(12, 33) if (k + g) % 32 == 0), 32)
+        route = self.get_option("fmn_eig_route")
+        jacobi = route == 1 or (route == 0 and n <= 512 and (2 * (k + guard) > n or n <= 128))
+        bound = torch.clamp(torch.diagonal(A, dim1=1, dim2=2).abs().amax(dim=1), min=1e-300)
+        lam = torch.empty((B, k), dtype=torch.float64, device=self.device)
+        V = torch.empty((B, n, k), dtype=torch.float64, device=self.device)
+        resid = torch.empty((B,), dtype=torch.float64, device=self.device)
+
+        def refuse(rounds):
+            return _lib.DenseMatchError(f"eigh_smallest: residual {resid.max().item():.3e} above {tol:g} * max |A_ii| = "
+                                        f"{tol * bound.min().item():.3e} after {rounds} rounds")
+        if jacobi:
+            if n > 512:
+                raise ValueError(f"eigh_smallest: the Jacobi route takes n <= 512, not {n}")
+            X = torch.eye(n, dtype=torch.float64, device=self.device).repeat(B, 1, 1).contiguous()
+            self._chk(self.lib.dm_eigh_smallest(self.ctx, B, n, _ptr(A), n, k, n - k, 1, 2, 2, _ptr(X), _ptr(lam), _ptr(V), _ptr(resid)))
+            if not bool((resid <= tol * bound).all()):
+                raise refuse(0)
+            return (lam[0], V[0], resid[0], 0) if single else (lam, V, resid, 0)
+        if 2 * (k + guard) > n:                     # (the block may not reach past the middle of the spectrum: see eigenbasis)
+            guard = n // 2 - k
+        if guard < 4 or k + guard > 512:
+            raise ValueError(f"eigh_smallest: the filtered route needs 2 (k + 4) <= n and k + guard <= 512 (k = {k}, n = {n})")
+        m = k + guard
+        g = torch.Generator(device=self.device).manual_seed(0)
+        X = torch.randn((n, m), dtype=torch.float64, device=self.device, generator=g).repeat(B, 1, 1).contiguous()
+        lam_w, V_w, resid_w = torch.empty_like(lam), torch.empty_like(V), torch.empty_like(resid)
+        done = torch.zeros((B,), dtype=torch.bool, device=self.device)
+        rounds = 0
+        for rounds in range(1, max_rounds + 1):
+            n_iter = 5 if rounds == 1 else 2
+            self._chk(self.lib.dm_eigh_smallest(self.ctx, B, n, _ptr(A), n, k, guard, n_iter, degree, 0 if rounds == 1 else 1, _ptr(X),
+                                                _ptr(lam_w), _ptr(V_w), _ptr(resid_w)))
+            ok = resid_w <= tol * bound
+            take = ~done if rounds == max_rounds else (ok & ~done)
+            if B == 1:
+                if bool(take[0]):
+                    lam, V, resid = lam_w.clone(), V_w.clone(), resid_w.clone()
+            else:
+                lam[take], V[take], resid[take] = lam_w[take], V_w[take], resid_w[take]
+            done |= ok
+            if bool(done.all()):
+                break
+        if not bool(done.all()):
+            raise refuse(max_rounds)
+        return (lam[0], V[0], resid[0], rounds) if single else (lam, V, resid, rounds)
+
+    def _fmn_maps(self, maps, M, who):
+        maps = self._dev(maps, torch.float64, "maps")
+        if maps.dim() != 3 or maps.shape[1] != maps.shape[2] or maps.shape[0] == 0:
+            raise ValueError(f"{who}: maps must be (E, ldm, ldm) with E >= 1")
+        if not 0 < M <= maps.shape[1]:
+            raise ValueError(f"{who}: M = {M} must lie in [1, {maps.shape[1]}]")
+        return maps
+
+    def fmn_orth_defect(self, maps, M):
+        """|FM^T FM - I|_F of the leading M x M block of every map (E, ldm, ldm) -> (E,) f64 (dm_fmn_orth_defect; FMN.set_isometries)"""
+        maps = self._fmn_maps(maps, int(M), "fmn_orth_defect")
+        out = torch.empty((maps.shape[0],), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.dm_fmn_orth_defect(self.ctx, maps.shape[0], int(M), _ptr(maps), maps.shape[1], _ptr(out)))
+        return out
+
+    def fmn_cycle_costs(self, maps, M, cyc_edges):
+        """cost of every three-cycle (n_cyc, 3) int32 = edge indices (e_ij, e_jk, e_ki): the maximum over its three rotations of
+        |C_a C_b C_c - I|_F on the leading M x M blocks -> (n_cyc,) f64 (dm_fmn_cycle_costs; FMN.get_cycle_weight)"""
+        maps = self._fmn_maps(maps, int(M), "fmn_cycle_costs")
+        if not isinstance(cyc_edges, torch.Tensor):
+            cyc_edges = torch.as_tensor(cyc_edges)
+        if cyc_edges.dim() != 2 or cyc_edges.shape[1] != 3:
+            raise ValueError("fmn_cycle_costs: cyc_edges must be (n_cyc, 3)")
+        bad = cyc_edges.shape[0] and (int(cyc_edges.min()) < 0 or int(cyc_edges.max()) >= maps.shape[0])   # (read where the list is)
+        cyc = self._dev(cyc_edges, torch.int32, "cyc_edges")
+        if bad:
+            raise ValueError(f"fmn_cycle_costs: cycle edge indices must lie in [0, {maps.shape[0]})")
+        out = torch.empty((cyc.shape[0],), dtype=torch.float64, device=self.device)
+        if cyc.shape[0]:
+            self._chk(self.lib.dm_fmn_cycle_costs(self.ctx, maps.shape[0], int(M), _ptr(maps), maps.shape[1], cyc.shape[0], _ptr(cyc), _ptr(out)))
+        return out
+
+    def fmn_quad_form(self, n, M, maps, edges, w):
+        """the quadratic form of the consistent latent basis, dense (n M, n M) f64 (dm_fmn_quad_form; CLB_quad_form): edges (E, 2) int32,
+        w (E,) f64 weights, maps (E, ldm, ldm)"""
+        n, M = int(n), int(M)
+        maps = self._fmn_maps(maps, M, "fmn_quad_form")
+        if not isinstance(edges, torch.Tensor):
+            edges = torch.as_tensor(edges)
+        if edges.numel() and (int(edges.min()) < 0 or int(edges.max()) >= n):       # (read where the edge list is: the host's for FMN)
+            raise ValueError(f"fmn_quad_form: edge ends must lie in [0, {n})")
+        edges = self._dev(edges, torch.int32, "edges")
+        w = self._dev(w, torch.float64, "w")
+        E = maps.shape[0]
+        if edges.shape != (E, 2) or w.shape != (E,):
+            raise ValueError("fmn_quad_form: edges must be (E, 2) and w (E,)")
+        if n * M > self.FMN_MAX_DIM or M > self.FMN_MAX_M:
+            raise ValueError(f"fmn_quad_form: n M = {n * M} (limit {self.FMN_MAX_DIM}), M = {M} (limit {self.FMN_MAX_M})")
+        W = torch.empty((n * M, n * M), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.dm_fmn_quad_form(self.ctx, n, E, M, _ptr(maps), maps.shape[1], _ptr(edges), _ptr(w), _ptr(W)))
+        return W
+
+    def fmn_cclb(self, CLB, evals, m):
+        """canonical consistent latent basis (dm_fmn_cclb; FMN.compute_CCLB): CLB (n, M, M), evals (n, >= M) the meshes' eigenvalues ->
+        (CCLB (n, M, m), cclb_eigenvalues (m,)) f64"""
+        CLB = self._dev(CLB, torch.float64, "CLB")
+        evals = self._dev(evals, torch.float64, "evals")
+        n, M, _ = CLB.shape
+        m = int(m)
+        if CLB.shape[2] != M or evals.dim() != 2 or evals.shape[0] != n or evals.shape[1] < M or not 0 < m <= M:
+            raise ValueError("fmn_cclb: CLB must be (n, M, M), evals (n, >= M) and 1 <= m <= M")
+        cclb = torch.empty((n, M, m), dtype=torch.float64, device=self.device)
+        ev = torch.empty((m,), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.dm_fmn_cclb(self.ctx, n, M, m, _ptr(CLB), _ptr(evals), evals.shape[1], _ptr(cclb), _ptr(ev)))
+        return cclb, ev
 
     def scratch(self, name, shape, dtype):
         """a device tensor that belongs to this engine and is handed out again by the next call with the same name, shape and dtype: for

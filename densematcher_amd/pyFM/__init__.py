@@ -6,3 +6,4 @@ NumPy out; the arithmetic runs in libdensematch (HIP, gfx950) through densematch
 from . import spectral, refine, signatures  # noqa: F401
 from .functional import FunctionalMapping  # noqa: F401
 from .mesh import TriMesh  # noqa: F401
+from .FMN import FMN, CLB_quad_form  # noqa: F401

@@ -91,6 +91,10 @@ size_t dm_workspace_bytes(const dm_ctx* ctx);
  *   "graph_geod_device" 1 | 0   shortest paths along the mesh edges in the Python layer (the default TriMesh.extract_fps / extract_fps_many,
  *                           get_geodesic(dijkstra=True), geometry.geodesic_distmat_dijkstra): dm_fps_graph / dm_graph_geodesic | SciPy's
  *                           Dijkstra on the host.  The library only keeps the value.  The two settings agree bit for bit.
+ *   "fmn_eig_route" 0 | 1 | 2   the eigenproblem of a functional map network in the Python layer (MatchEngine.eigh_smallest, FMN.compute_CLB):
+ *                           by the sizes (Jacobi where the filtered iteration has no room, 2 (k + guard) > n, or n <= 128) | always the
+ *                           full Jacobi eigendecomposition (n <= 512) | always the Chebyshev-filtered iteration.  The library only keeps
+ *                           the value.  The routes agree on eigenvalues and invariant subspaces, not on bits.
  *   "p2pfm_direct"  1 | 0   dm_p2p_to_fm (and the p2p_to_FM steps of dm_zoomout / dm_icp): register-resident tiles, operands straight
  *                           from global memory, fixed-order in-workgroup reduction | LDS-staged 64 x 64 tiles + split-K partials + reduce
  *   "simnn1_wt"     4 | 2   tile shape of the fused ZoomOut search: 8 waves, 256 x 256 | 4 waves, 128 x 256 (two workgroups per CU)
@@ -383,6 +387,37 @@ int dm_p2p_to_fm_f64(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
 int dm_eigenbasis(dm_ctx* ctx, int B, int N, int nnz, const int32_t* ell_cols, const double* ell_vals, const float* mass,
                   int k, int guard, int n_iter, int degree, int warm_start,
                   double* X, double* lam, double* Phi, double* resid);
+
+/* ---- dense symmetric eigenproblem ---------------------------------------------------------------------------------------
+ * The k smallest eigenpairs of B dense symmetric matrices A (B,n,lda) fp64 (only the symmetric part is meaningful: the Gershgorin bound
+ * reads columns as rows).  Replaces scipy.sparse.linalg.eigsh(W, k, which='LM', sigma=-1e-6) of the functional map network
+ * (pyFM/FMN/FMN.py:293-334), whose W is block-dense.  Same contract as dm_eigenbasis -- Chebyshev-filtered subspace iteration, Rayleigh-Ritz
+ * by the Jacobi eigensolver, Cholesky-QR / polar orthonormalisation -- without mass scaling: X (B,n,k+guard) in/out (warm_start = 0: a random
+ * block, 1: the block a previous call returned, 2: the identity with k + guard = n <= 512, one Jacobi eigendecomposition of A itself),
+ * lam (B,k) ascending, V (B,n,k) orthonormal columns (sign: largest entry of a column positive), resid (B) = max_j |A x_j - lam_j x_j|.
+ * Limits: n <= 4096, k + guard <= min(n, 512); anything else is DM_EINVAL. */
+int dm_eigh_smallest(dm_ctx* ctx, int B, int n, const double* A, int lda, int k, int guard, int n_iter, int degree, int warm_start,
+                     double* X, double* lam, double* V, double* resid);
+
+/* ---- functional map networks (pyFM/FMN/FMN.py) -----------------------------------------------------------------------------
+ * A network has n shapes and E directed edges; edge e = (i, j) carries the map maps[e] (stored ldm x ldm, row stride ldm, fp64), of which
+ * the leading M x M block is used (M <= ldm, M <= 256).  Every sum runs in a fixed order and an edge's / cycle's result does not depend
+ * on what else is in the call.
+ *   dm_fmn_orth_defect  out[e] = |FM^T FM - I|_F of the cropped map (FMN.set_isometries, :234-270).
+ *   dm_fmn_cycle_costs  cyc_edges (n_cyc,3) int32 = the edge indices (e_ij, e_jk, e_ki) of a three-cycle; cost[c] = the maximum over the
+ *                       three rotations of |C_a C_b C_c - I|_F (FMN.get_cycle_weight, :559-594).  The caller validates the indices (MatchEngine.fmn_cycle_costs raises
+ *                       ValueError); the kernel clamps an index outside [0, E) so that it never reads outside maps.
+ *   dm_fmn_quad_form    W (n M x n M, row stride n M) = the quadratic form of the consistent latent basis (CLB_quad_form, :690-738): per
+ *                       edge e = (i, j) with weight w[e], block (i,i) += w FM^T FM, (j,j) += w I, (i,j) -= w FM^T, (j,i) -= w FM, the edges
+ *                       added in index order; every block is written, zeros included.  edges (E,2) int32; the caller validates the ends (MatchEngine.fmn_quad_form
+ *                       raises ValueError); an edge with an end outside [0, n) writes nothing.
+ *   dm_fmn_cclb         canonical consistent latent basis (FMN.compute_CCLB, :336-369): E = sum_i Y_i^T diag(evals[i][:M]) Y_i with
+ *                       Y_i = CLB[i][:, :m] (CLB (n,M,M), evals (n,ldl)), symmetrised; (theta, Q) = eigenpairs of E / n ascending (Jacobi, theta as
+ *                       Rayleigh quotients of the computed vectors; sign: largest entry of a column of Q positive); cclb[i] = Y_i Q (n,M,m), cclb_evals (m).  m <= M <= 256. */
+int dm_fmn_orth_defect(dm_ctx* ctx, int E, int M, const double* maps, int ldm, double* out);
+int dm_fmn_cycle_costs(dm_ctx* ctx, int E, int M, const double* maps, int ldm, int n_cyc, const int32_t* cyc_edges, double* cost);
+int dm_fmn_quad_form(dm_ctx* ctx, int n, int E, int M, const double* maps, int ldm, const int32_t* edges, const double* w, double* W);
+int dm_fmn_cclb(dm_ctx* ctx, int n, int M, int m, const double* CLB, const double* evals, int ldl, double* cclb, double* cclb_evals);
 
 /* The linear assignments of mapped indicators WITHOUT the dense matrices (functional_map.py:57, 78 call
  * scipy.optimize.linear_sum_assignment(mapped_indicator, maximize=True) on the N2 x N1 matrix of pyFM/spectral/convert.py:144).  For maps
