@@ -749,7 +749,8 @@ extern "C" int dm_fmap_fit_fused_ok(int k1, int k2, const double* weights /*host
 extern "C" int dm_fmap_fit_fused(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1, const float* Phi2,
                                  int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1, const double* lam2,
                                  const double* weights, int m, const double* x0, double ftol, double pgtol, int maxiter, int maxfun,
-                                 int maxls, double* x_out, double* f_out, int32_t* info_out, double* grad_out, int* evaluations_out) {
+                                 int maxls, int element_f32, double* x_out, double* f_out, int32_t* info_out, double* grad_out,
+                                 int* evaluations_out) {
     if (!ctx) return DM_EINVAL;
     DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && k1 > 0 && k2 > 0 && D > 0, "sizes must be positive");
     DM_REQUIRE(ctx, Phi1 && Phi2 && mass1 && A && Bm && lam1 && lam2 && weights && x0 && f_out, "null pointer");
@@ -795,7 +796,7 @@ extern "C" int dm_fmap_fit_fused(dm_ctx* ctx, int B, int N1, int N2, int k1, int
     choose(B);
     p.n_active = B;
     DM_REQUIRE(ctx, (long long)B * p.nU < (1ll << 31), "batch too large for one launch");
-    const bool f32 = ctx->opt_fit_f32 != 0;                    // dm_set_option("fit_f32"): the element loop in the reference's precision
+    const bool f32 = element_f32 != 0;                         // the element loop in the reference's precision
     const size_t bPsi32 = f32 ? (size_t)B * p.N1pad * KL1 * 4 : 0;
     const size_t bPsi = (size_t)B * p.N1pad * KL1 * 8, bSums = (size_t)B * FF_SUMS * 8, bPQ = (size_t)B * (k1 + k2) * k1 * 8;
     const size_t bUnit = (size_t)B * p.nU * np1 * 8, bChunk = (size_t)B * p.nchunks * np1 * 8;

@@ -14,8 +14,9 @@
 #include "densematch.h"
 
 // (abi N: bumped whenever an existing entry point changes what it reads or writes -- abi 5: dm_fmap_energy_grad / dm_fmap_fit_steps read TEN
-//  weights (w_area, w_conformal appended in round 4); dm_eigenbasis warm_start = 2; dm_laplacian_*, dm_fmap_fit_fused added)
-#define DM_VERSION_STRING "densematch 0.5.0 (gfx950, abi 5)"
+//  weights (w_area, w_conformal appended in round 4); dm_eigenbasis warm_start = 2; dm_laplacian_*, dm_fmap_fit_fused added; abi 6: dm_fmap_fit_fused takes the element loop's precision
+//  as the argument element_f32, the option "fit_f32" is gone)
+#define DM_VERSION_STRING "densematch 0.5.0 (gfx950, abi 6)"
 
 struct dm_ctx {
     int device = 0;
@@ -43,7 +44,6 @@ struct dm_ctx {
     int opt_solve_packed = 0;    // 1: the packed-storage solver for every system size it supports
     int opt_proj_onepass = 1;    // 1: the fp16-split projection reads the basis once (running scale per workgroup); 0: maxima pass + fp32 copy + r03 tile kernel
     int opt_fit_mfma = 1;        // fp32 element loop of dm_fmap_fit_fused, maps up to 16 x 16: the two products of an entry on v_mfma_f32_16x16x4_f32 (1) or on the packed vector FMA (0); both agree with the oracle to the same 1e-7
-    int opt_fit_f32 = 0;         // 1: dm_fmap_fit_fused runs its element loop in fp32 (the reference's precision), 0: float64
     int opt_simnn_prio = 0;      // 1: the tile kernels raise their wave priority around the matrix instructions (s_setprio)
     int opt_simnn_big = 0;       // 1: the tile kernels run four waves of 128 x 128 (accumulators in AGPRs) instead of eight of 128 x 64
     int opt_simnn_band = 4;      // tile rows per band of the similarity kernels' tile order (0: row-major); 4 measured best at

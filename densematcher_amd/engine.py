@@ -131,15 +131,16 @@ class MatchEngine:
         self.stream.synchronize()
 
     OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0, "energy_keep_gram": 0,
-                       "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_f32": 0, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
+                       "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
                        "zoomout_sub_fused": 1, "fps_heat_route": 0, "graph_geod_device": 1, "fmn_eig_route": 0}
 
     def set_option(self, name, value):
         """Choose between code paths of the library (include/densematch.h: dm_set_option).  Most settings return the same
-        results bit for bit; "solve_pcg" (the batched iteration in front of the direct solvers) changes bits: its C agrees with
+        results bit for bit; four change bits -- "solve_pcg", "fit_mfma", "zoomout_sub_fused" and "fmn_eig_route".  "solve_pcg" (the
+        batched iteration in front of the direct solvers): its C agrees with
         solve_pcg = 0 to max(1e-9, 4 (n + D) u kappa) relative per system of condition number kappa (u = 2^-53,
-        tests/test_gpu_solver_conditioning.py); "fit_f32" runs the fused fit's element loop in fp32 (the reference's precision) and
-        "fit_mfma" chooses the summation order of its products, so both change the fused fit's bits; "zoomout_sub_fused" chooses
+        tests/test_gpu_solver_conditioning.py); "fit_mfma" chooses the summation order of the products in the fused fit's fp32
+        element loop (fitted maps within 1e-6 of each other); "zoomout_sub_fused" chooses
         between the one-factor device loop of subsampled ZoomOut (1) and the host-chained least-squares steps (0): the maps agree
         to 1e-9, not bit for bit; "graph_geod_device" chooses between the device kernels (1) and SciPy's Dijkstra on the host (0) for
         shortest paths along mesh edges (the default extract_fps / extract_fps_many, get_geodesic(dijkstra=True)): the two settings
@@ -505,14 +506,10 @@ class MatchEngine:
         fo = torch.empty((B,), dtype=torch.float64, device=self.device)
         info = torch.empty((B, 4), dtype=torch.int32, device=self.device)
         nev = C.c_int(0)
-        self.set_option("fit_f32", 1 if f32 else 0)
-        try:
-            self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
-                                                 _ptr(lam2), C.cast(w, C.c_void_p), int(opts["maxcor"]), _ptr(x0d), float(opts["ftol"]), float(opts["gtol"]),
-                                                 int(maxiter), int(opts["maxfun"]), int(opts["maxls"]), _ptr(xo), _ptr(fo), _ptr(info), C.c_void_p(0),
-                                                 C.byref(nev)))
-        finally:
-            self.set_option("fit_f32", 0)
+        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
+                                             _ptr(lam2), C.cast(w, C.c_void_p), int(opts["maxcor"]), _ptr(x0d), float(opts["ftol"]), float(opts["gtol"]),
+                                             int(maxiter), int(opts["maxfun"]), int(opts["maxls"]), 1 if f32 else 0, _ptr(xo), _ptr(fo), _ptr(info),
+                                             C.c_void_p(0), C.byref(nev)))
         info = info.cpu().numpy()
         info[:, 0] = np.where(info[:, 0] == 0, 4, info[:, 0])
         res = types.SimpleNamespace(x=xo.cpu().numpy(), fun=fo.cpu().numpy(), status=info[:, 0].copy(), nit=info[:, 1].copy(),
@@ -539,13 +536,11 @@ class MatchEngine:
         w = self._weight_array(dict(weights, w_dcomm=0.0))
         energy = torch.empty((B,), dtype=torch.float64, device=self.device)
         grad = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
-        self.set_option("fit_f32", 1 if precision == "f32" else 0)
-        try:
-            self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
-                                                 _ptr(lam2), C.cast(w, C.c_void_p), 0, _ptr(Cm), 0.0, 0.0, 0, 0, 0, C.c_void_p(0), _ptr(energy), C.c_void_p(0),
-                                                 _ptr(grad), None))
-        finally:
-            self.set_option("fit_f32", 0)
+        if precision not in ("f32", "f64"):
+            raise ValueError("precision must be 'f32' or 'f64'")
+        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
+                                             _ptr(lam2), C.cast(w, C.c_void_p), 0, _ptr(Cm), 0.0, 0.0, 0, 0, 0, 1 if precision == "f32" else 0,
+                                             C.c_void_p(0), _ptr(energy), C.c_void_p(0), _ptr(grad), None))
         return energy, grad
 
     def fit_general(self, batch, weights, x0, k=None, maxiter=15000, lbfgs_options=None, driver="device", check_every=4, orient_ops=None, fused=True,
@@ -595,6 +590,7 @@ class MatchEngine:
         ints = state[n_f64:n_f64 + (8 * B * 4 + 7) // 8].view(torch.int32)[:8 * B].view(B, 8)
         nev, maxfun = 0, int(opts["maxfun"])
         # the projected descriptors A, Bm are fixed during the fit: their Gram blocks are computed by the first evaluation only
+        keep_gram = self.get_option("energy_keep_gram")
         self.set_option("energy_keep_gram", 1)
         # the evaluation loop itself runs behind the ABI, `check_every` evaluations per call (dm_fmap_fit_steps): a Python round per
         # evaluation cost more host time than the evaluation takes on the device for one small pair
@@ -609,7 +605,7 @@ class MatchEngine:
                 if bool((ints[:, 0] != 0).all()) or nev > maxfun + 2:        # (one host synchronisation per check_every evaluations)
                     break
         finally:
-            self.set_option("energy_keep_gram", 0)
+            self.set_option("energy_keep_gram", keep_gram)         # (the caller's setting; setting it drops what this fit kept)
         xo = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
         fo = torch.empty((B,), dtype=torch.float64, device=self.device)
         info = torch.empty((B, 4), dtype=torch.int32, device=self.device)

@@ -6,50 +6,38 @@ import time
 
 import numpy as np
 
-from .pyFM.functional import FunctionalMapping
-from .pyFM.mesh import TriMesh
+from .pyFM.functional import FunctionalMapping, fit_models, fit_parameters
+from .pyFM.mesh import TriMesh, laplacian
 
 
 def _np(x):
     return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
 
 
-def _assign(matrix):
-    """scipy.optimize.linear_sum_assignment(matrix, maximize=True) (functional_map.py:57,66,78; eta == 1 after fit) on the GPU:
-    same algorithm and tie rules as SciPy, identical (row_ind, col_ind).  `matrix`: a MappedIndicator or a device tensor."""
-    from .engine import default_engine
-    eng = default_engine()
-    dev = matrix.device_tensor() if hasattr(matrix, "device_tensor") else matrix
-    if dev.dim() == 2:
-        dev = dev[None]
-    col = eng.linear_sum_assignment(dev, maximize=True)[0].cpu().numpy().astype(np.int64)
+def _matched(col):
+    """(row_ind, col_ind) of an assignment given as the column of every row (-1: none), as scipy.optimize.linear_sum_assignment returns them"""
     rows = np.nonzero(col >= 0)[0]
     return rows, col[rows]
 
 
 def _assign_early(matrix, slot):
-    """_assign started NOW on a side stream (its own MatchEngine), while the caller goes on with the main stream: returns the
-    function that waits for it and hands back (row_ind, col_ind).  compute_surface_map's three assignments do not depend on each
+    """scipy.optimize.linear_sum_assignment(matrix, maximize=True) (functional_map.py:57,66,78; eta == 1 after fit) started NOW on a side
+    stream (its own MatchEngine), while the caller goes on with the main stream: returns the function that waits for it and hands back
+    (row_ind, col_ind).  `matrix`: a MappedIndicator or a device tensor.  compute_surface_map's three assignments do not depend on each
     other (functional_map.py:57, 66, 78), and the longest -- the fitted map's indicator, 20 ms on one workgroup -- can start as soon
     as the fit is done, beside the precise map, ICP and the vertex maps of the refined map."""
     import torch
     from .engine import default_engine
     dev_index = torch.cuda.current_device()
-    main = torch.cuda.current_stream(dev_index)
     side = _side_streams(dev_index, slot + 1)[slot]
     dev = matrix.device_tensor() if hasattr(matrix, "device_tensor") else matrix       # (formed on the main stream)
     if dev.dim() == 2:
         dev = dev[None]
-    side.wait_stream(main)
-    with torch.cuda.stream(side):
-        dev.record_stream(side)
-        done = default_engine().linear_sum_assignment(dev, maximize=True, defer=True)
+    done = _on_side_stream(side, (dev,), lambda: default_engine().linear_sum_assignment(dev, maximize=True, defer=True))
 
     def finish():
         with torch.cuda.stream(side):
-            col = done()[0].cpu().numpy().astype(np.int64)
-        rows = np.nonzero(col >= 0)[0]
-        return rows, col[rows]
+            return _matched(done()[0].cpu().numpy().astype(np.int64))
     return finish
 
 
@@ -95,28 +83,7 @@ def _assign_many(matrices):
             col = np.stack([eng.linear_sum_assignment(d[None], maximize=True)[0].cpu().numpy() for d in devs]).astype(np.int64)
         else:
             col = eng.linear_sum_assignment(torch.stack(devs), maximize=True).cpu().numpy().astype(np.int64)
-    out = []
-    for c in col:
-        rows = np.nonzero(c >= 0)[0]
-        out.append((rows, c[rows]))
-    return out
-
-
-class _robust_backend_for_call:
-    """robust_backend='restated' | 'wheel' for the duration of one call (None: whatever laplacian.set_robust_backend / the environment say)"""
-    def __init__(self, name):
-        self.name = name
-
-    def __enter__(self):
-        from .pyFM.mesh import laplacian
-        self.prev = laplacian.robust_backend()
-        if self.name is not None:
-            laplacian.set_robust_backend(self.name)
-
-    def __exit__(self, *exc):
-        from .pyFM.mesh import laplacian
-        laplacian.set_robust_backend(self.prev)
-        return False
+    return [_matched(c) for c in col]
 
 
 def compute_surface_map(mesh1_t, mesh2_t, c1, c2, n_ev=50, compute_extra=False, optimizer="fmin_l_bfgs_b", descr_type="neural",
@@ -135,6 +102,7 @@ def compute_surface_map(mesh1_t, mesh2_t, c1, c2, n_ev=50, compute_extra=False, 
     p2p_21 / p2p_12 are the indicator arg-max maps (:49-50), the *_adjoint ones the kd-tree maps (:48).
     '''
     assert descr_type in ["neural", "HKS", "WKS"]
+    laplacian.check_robust_backend(robust_backend)
     mesh1 = TriMesh(_np(mesh1_t.verts_list()[0]), _np(mesh1_t.faces_list()[0]))
     mesh2 = TriMesh(_np(mesh2_t.verts_list()[0]), _np(mesh2_t.faces_list()[0]))
     if descr_type == "neural":
@@ -144,8 +112,7 @@ def compute_surface_map(mesh1_t, mesh2_t, c1, c2, n_ev=50, compute_extra=False, 
         process_params = {'n_ev': (n_ev, n_ev), 'n_descr': 16 if descr_type == "HKS" else 2048, 'landmarks': None,
                           'descr_type': descr_type, 'subsample_step': 1, 'signature_route': signature_route}
     model = FunctionalMapping(mesh1, mesh2, partial=False, optimizer=optimizer)
-    with _robust_backend_for_call(robust_backend):
-        model.preprocess(**process_params, verbose=False)
+    model.preprocess(**process_params, verbose=False, robust_backend=robust_backend)
     fit_params = dict(fit_params or {})
     fit_params.pop("verbose", None)
     model.fit(**fit_params)
@@ -208,9 +175,10 @@ def _on_side_stream(side, tensors, launch):
         return launch()
 
 
-def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenbases=None, lsa_streams=None):
+def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenbases=None, lsa_streams=None, robust_backend=None):
     """the pairs `idx` of a batch on the CURRENT stream's engine: eigenbases of their 2 len(idx) meshes in one batched solve, then per group
-    of equal sizes one device L-BFGS, one call per map stage, all assignments of the group side by side"""
+    of equal sizes one fit (fit_models), one call per map stage, all assignments of the group side by side.  fit_params: checked
+    (fit_parameters)"""
     import torch
     from .engine import default_engine
     from .pyFM.spectral.convert import MappedIndicator, _real_dtype
@@ -263,7 +231,7 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
     try:
         # ---- eigenbases: every mesh of the chunk in one batched solve (FunctionalMapping.preprocess: functional.py:300-301)
         all_meshes = [m for i in idx for m in (models[i].mesh1, models[i].mesh2)]
-        type(all_meshes[0]).process_many(all_meshes, [n_ev] * len(all_meshes), robust=True)
+        type(all_meshes[0]).process_many(all_meshes, [n_ev] * len(all_meshes), robust=True, robust_backend=robust_backend)
     finally:
         if after_eigenbases is not None:
             after_eigenbases()
@@ -297,37 +265,7 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
                "a1": eng._dev(a1.astype(np.float32), torch.float32, "a1"), "a2": eng._dev(a2.astype(np.float32), torch.float32, "a2"),
                "lam1": eng._dev(lam1, torch.float64, "lam1"), "lam2": eng._dev(lam2, torch.float64, "lam2"),
                "F1": eng._dev(F1d, tdt[fdt], "F1"), "F2": eng._dev(F2d, tdt[fdt], "F2")}
-        fp = dict(w_descr=1e-1, w_lap=1e-3, w_dcomm=1, w_p2p=0, w_stochastic=0, w_ent=0, w_range01=0, w_sumto1=0, w_area=0, w_conformal=0,
-                  optinit="zeros", maxiter=1000000, stopping="reference", w_orient=0, orient_reversing=False, orient_route="device")
-        fp.update({k_: v for k_, v in fit_params.items() if k_ in fp})
-        general = {n: fp[n] for n in ("w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal")}
-        from .pyFM.functional import CLOSED_FORM_MAX_K1
-        wide = n_ev > CLOSED_FORM_MAX_K1              # (FunctionalMapping.fit: maps wider than the closed form's solvers take the iterative scheme, tight)
-        if any(v > 0 for v in general.values()) or fp["w_orient"] > 0 or wide:
-            from .pyFM.functional import LBFGS_OPTIONS, LBFGS_WIDE
-            x0 = np.stack([m.get_x0(optinit=fp["optinit"]) for m in g])
-            weights = dict(w_descr=fp["w_descr"], w_lap=fp["w_lap"], **general)
-            orient_ops = None
-            if fp["w_orient"] > 0:
-                # FunctionalMapping.fit's rescaling (functional.py:432-456) for the whole group: the operators of both forms, the two
-                # energies at x0, then every pair's own weight
-                (o1, o2), orient_ops = _group_orientation_ops(eng, g, (Phi1, Phi2), (dev["F1"], dev["F2"]), n_ev, fp["orient_route"], fp["orient_reversing"])
-                e_native = eng.fit_energy(dev, dict(weights, w_orient=0.0), x0)
-                e_orient = eng.fit_energy(dev, dict(w_orient=1.0), x0, orient_ops=(o1, o2))
-                w_orient = [fp["w_orient"] * float(e_native[q]) / float(e_orient[q]) for q in range(nb)]
-                for q, m in enumerate(g):
-                    m.w_orient_rescaled = w_orient[q]
-                weights["w_orient"] = np.asarray(w_orient, dtype=np.float64)
-            C0, res = eng.fit_general(dev, weights, x0, maxiter=fp["maxiter"],
-                                      lbfgs_options=LBFGS_WIDE if wide else (LBFGS_OPTIONS if fp["stopping"] == "tight" else None),
-                                      orient_ops=orient_ops)
-            C0 = np.asarray(C0, dtype=np.float64)
-        else:
-            res = None
-            A = eng.project(dev["Phi1"], dev["a1"], dev["F1"])
-            Bm = eng.project(dev["Phi2"], dev["a2"], dev["F2"])
-            c00 = eng.c00(Phi1, Phi2, a1, a2)
-            C0 = eng.fmap_solve(A, Bm, dev["lam1"], dev["lam2"], c00, fp["w_descr"], fp["w_lap"], check=True).cpu().numpy()
+        C0, _ = fit_models(eng, g, fit_params, dev, (Phi1, Phi2, a1, a2))
         # ---- vertex maps of the fitted map, precise map, ICP, vertex maps of the ICP map: one call each for the group
         _, P1, P2, A1d = eng._reals(Phi1, Phi2, a1)
         C0d = eng._dev(C0, torch.float64, "C")
@@ -397,60 +335,19 @@ def _batch_chunk(models, idx, out, n_ev, compute_extra, fit_params, after_eigenb
             else:
                 cols = eng.linear_sum_assignment(torch.cat(mats, dim=0) if len(mats) > 1 else mats[0], maximize=True).cpu().numpy().astype(np.int64)
 
-        def assignment(c):
-            rows = np.nonzero(c >= 0)[0]
-            return rows, c[rows]
         h = {n: v.cpu().numpy().astype(np.int64) for n, v in maps0.items()}
         hi = {n: v.cpu().numpy().astype(np.int64) for n, v in mapsi.items()}
         Ci_h = Ci.cpu().numpy()
         for q, i in enumerate(gidx):
             model = g[q]
-            model.FM = C0[q]
             model._FM_icp = Ci_h[q]
             model.FM_type = "icp"
-            model.eta = np.ones(model.mesh2.n_vertices)
-            if res is not None:
-                import types
-                model.fit_result = types.SimpleNamespace(nit=res.nit[q:q + 1], nfev=res.nfev[q:q + 1], fun=res.fun[q:q + 1],
-                                                         status=res.status[q:q + 1], message=res.message[q:q + 1])
             model.mapped_indicator = MappedIndicator(eng, P1[q:q + 1], P2[q:q + 1], A1d[q:q + 1], Ci[q:q + 1], hi["ind21"][q], hi["ind12"][q])
-            hung = assignment(cols[q]) if compute_extra else None
-            hung_p = assignment(cols[nb + q]) if compute_extra else None
-            hung_i = assignment(cols[(2 * nb if compute_extra else 0) + q])
+            hung = _matched(cols[q]) if compute_extra else None
+            hung_p = _matched(cols[nb + q]) if compute_extra else None
+            hung_i = _matched(cols[(2 * nb if compute_extra else 0) + q])
             out[i] = (h["ind21"][q], h["ind12"][q], hung, hung_p, hi["ind21"][q], hi["ind12"][q], hung_i, model, model.mesh1, model.mesh2,
                       h["knn21"][q], h["knn12"][q], hi["knn21"][q], hi["knn12"][q])
-
-
-def _group_orientation_ops(eng, g, Phis, Fs, n_ev, route, reversing):
-    """the orientation operators of a group of models, both forms FunctionalMapping.fit uses: ((o1, o2) the rescaling operators -- rows
-    divided by vertex_areas, the second reversed on request --, (f1, f2) those of the optimisation -- rows divided by diag(A), never
-    reversed), each (nb, D, k, k).  Phis: the stacked bases in the meshes' own precision (what the single call's device route reads), Fs: the
-    descriptors as staged for the fit.  route "device": MatchEngine.orientation_ops on the stacked meshes (mesh 2's face count may
-    differ inside a group: padded, n_faces), the operators stay on the device; "host": the per-pair host operators, stacked."""
-    from .pyFM.functional import _orient_row_scale
-    if route == "host":
-        st = lambda ops, side: np.stack([np.stack([o[side] for o in ops_q]) for ops_q in ops])
-        resc = [m.compute_orientation_op(reversing=reversing) for m in g]
-        fit = [m.compute_orientation_op(reversing=False, area="mass") for m in g]
-        return (st(resc, 0), st(resc, 1)), (st(fit, 0), st(fit, 1))
-    vertex, same = [], True
-    for side, (Phi, F) in enumerate(zip(Phis, Fs)):
-        meshes = [(m.mesh1, m.mesh2)[side] for m in g]
-        verts = np.stack([np.asarray(m.vertlist, dtype=np.float64) for m in meshes])
-        nf = np.array([m.facelist.shape[0] for m in meshes], dtype=np.int32)
-        faces = np.zeros((len(meshes), int(nf.max()), 3), dtype=np.int32)
-        for q, m in enumerate(meshes):
-            faces[q, :nf[q]] = m.facelist
-        rs = [_orient_row_scale(m) for m in meshes]
-        scale = None
-        if any(r is not None for r in rs):
-            same = False
-            scale = np.stack([np.ones(m.n_vertices) if r is None else r for m, r in zip(meshes, rs)])
-        vertex.append((eng.orientation_ops(verts, faces, Phi, F, k=n_ev, row_scale=scale, n_faces=nf), (verts, faces, Phi, F, nf)))
-    (r1, _), (r2, _) = vertex
-    # (lumped masses ARE the vertex areas -- A diagonal: the two forms are the same operators, one call serves both)
-    fit = (r1, r2) if same else tuple(eng.orientation_ops(v, f, P, F, k=n_ev, n_faces=nf) for _, (v, f, P, F, nf) in vertex)
-    return (r1, -r2 if reversing else r2), fit
 
 
 def compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev=50, compute_extra=False, optimizer="fmin_l_bfgs_b", descr_type="neural",
@@ -467,17 +364,19 @@ def compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev=50, compute_e
     fills the vector ALUs, another's eigensolver (a chain of a thousand small launches), linear assignments (a workgroup per matrix,
     latency bound) and host-side bookkeeping run beside it.  Default: one chunk per 64 pairs, at most four (r05, float64 fit: 500 ms on one stream, 455 on two, 495 on three, 580 on four; r06, fp32 element loop and a one-chunk call's assignments started early: 260 / 255-297 / 267-308 ms on one / two / three).  A pair's results do
     not depend on the chunking.
-    robust_backend: as for compute_surface_map.  Two host threads may call concurrently when each calls on its own HIP stream."""
-    with _robust_backend_for_call(robust_backend):
-        out = _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_extra, optimizer, descr_type, maxiter, optimize_p2p,
-                                         fit_params, streams)
+    fit_params: FunctionalMapping.fit's parameters, checked and fitted by the code the single call runs (pyFM/functional.py: fit_parameters,
+    fit_plan, fit_models); orient_route defaults to "device" here, and the L-BFGS driver is always the device's.
+    robust_backend: as for compute_surface_map; an argument of this call, not a process-wide setting.  Two host threads may call
+    concurrently when each calls on its own HIP stream."""
+    out = _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_extra, optimizer, descr_type, maxiter, optimize_p2p,
+                                     fit_params, streams, robust_backend)
     for t in out:
         if t is not None:
             t[8].release_device_rows(); t[9].release_device_rows()
     return out
 
 
-def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_extra, optimizer, descr_type, maxiter, optimize_p2p, fit_params, streams):
+def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_extra, optimizer, descr_type, maxiter, optimize_p2p, fit_params, streams, robust_backend):
     import torch
     assert descr_type in ["neural", "HKS", "WKS"]
     B = len(meshes1_t)
@@ -485,18 +384,10 @@ def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_ext
     assert len(meshes2_t) == B and (spectral or (len(c1s) == B and len(c2s) == B))
     fit_params = dict(fit_params or {})
     fit_params.pop("verbose", None)
-    known = {"w_descr", "w_lap", "w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_area", "w_conformal", "optinit",
-             "maxiter", "stopping", "w_orient", "w_area_difference", "w_mumford_shah", "mumford_shah_var", "w_eta_entropy", "orient_reversing",
-             "orient_route", "device", "driver"}
-    unknown = set(fit_params) - known
-    if unknown:
-        raise TypeError(f"fit() got unexpected keyword arguments {sorted(unknown)}")
-    if any(fit_params.get(n, 0) > 0 for n in ("w_area_difference", "w_mumford_shah", "w_eta_entropy")):
-        raise NotImplementedError("area-difference / Mumford-Shah / eta-entropy terms are not on the accelerated path; pass 0")
-    if fit_params.get("orient_route", "device") not in ("host", "device"):
-        raise ValueError(f'orient_route must be "host" or "device", not {fit_params["orient_route"]!r}')
-    if fit_params.get("stopping", "reference") not in ("tight", "reference"):
-        raise ValueError("stopping must be 'tight' or 'reference'")
+    # FunctionalMapping.fit's parameters and checks; the operators of w_orient on the device unless the caller says otherwise, and the
+    # device's own L-BFGS driver always (driver="scipy" optimises one pair per call)
+    fit_params = fit_parameters({"orient_route": "device", **fit_params, "driver": "device"})
+    laplacian.check_robust_backend(robust_backend)
     timing = os.environ.get("TIMEIT", False)
     if timing:
         compute_extra = True
@@ -522,7 +413,7 @@ def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_ext
     dev_index = torch.cuda.current_device()
     if streams == 1:
         lsa_side = _side_streams(dev_index, 2)                                  # the two assignment streams
-        _batch_chunk(models, list(range(B)), out, n_ev, compute_extra, fit_params, lsa_streams=lsa_side)
+        _batch_chunk(models, list(range(B)), out, n_ev, compute_extra, fit_params, lsa_streams=lsa_side, robust_backend=robust_backend)
         return out
     from concurrent.futures import ThreadPoolExecutor
     from .shard import block_range
@@ -544,7 +435,8 @@ def _compute_surface_map_batch(meshes1_t, meshes2_t, c1s, c2s, n_ev, compute_ext
                 eig_done[c - 1].wait()
             side[c].wait_stream(caller)
             with torch.cuda.stream(side[c]):
-                _batch_chunk(models, list(range(lo, hi)), out, n_ev, compute_extra, fit_params, after_eigenbases=eig_done[c].set)
+                _batch_chunk(models, list(range(lo, hi)), out, n_ev, compute_extra, fit_params, after_eigenbases=eig_done[c].set,
+                             robust_backend=robust_backend)
             side[c].synchronize()
         finally:
             eig_done[c].set()                                             # (a chunk that failed must not leave the next one waiting)

@@ -26,6 +26,49 @@ LBFGS_OPTIONS = {"ftol": 1e-12, "gtol": 1e-9, "maxcor": 30, "maxfun": 15000}
 LBFGS_WIDE = {"ftol": 1e-15, "gtol": 1e-11, "maxcor": 30, "maxfun": 50000}
 
 
+# FunctionalMapping.fit's parameters and their defaults (functional.py:352-360, and what is not in the reference: stopping, driver,
+# orient_route).  compute_surface_map_batch's fit_params are the same names.  (fit keeps its explicit signature, like the reference's;
+# tests/test_fit_stage_cpu.py holds the two lists together.)
+FIT_DEFAULTS = dict(w_descr=1e-1, w_lap=1e-3, w_dcomm=1, w_orient=0, w_area=0, w_conformal=0, w_p2p=0, w_stochastic=0, w_ent=0, w_range01=0,
+                    w_sumto1=0, w_area_difference=0, w_mumford_shah=0, mumford_shah_var=0.1, w_eta_entropy=0, orient_reversing=False,
+                    optinit='zeros', verbose=False, maxiter=1000000, device=None, stopping="reference", driver="device", orient_route="host")
+_OFF_PATH_TERMS = ("w_area_difference", "w_mumford_shah", "w_eta_entropy")
+_ITERATIVE_TERMS = ("w_dcomm", "w_p2p", "w_stochastic", "w_ent", "w_range01", "w_sumto1", "w_orient", "w_area", "w_conformal")
+
+
+def fit_parameters(given):
+    """FIT_DEFAULTS with the caller's values, checked -- host code only, nothing here needs a device"""
+    unknown = set(given) - set(FIT_DEFAULTS)
+    if unknown:
+        raise TypeError(f"fit() got unexpected keyword arguments {sorted(unknown)}")
+    p = dict(FIT_DEFAULTS, **given)
+    if p["orient_route"] not in ("host", "device"):
+        raise ValueError(f'orient_route must be "host" or "device", not {p["orient_route"]!r}')
+    if p["optinit"] not in ('random', 'identity', 'zeros'):
+        raise ValueError(f"optinit arg should be 'random', 'identity' or 'zeros', not {p['optinit']}")
+    if p["stopping"] not in ("tight", "reference"):
+        raise ValueError("stopping must be 'tight' or 'reference'")
+    live = [n for n in _OFF_PATH_TERMS if p[n] > 0]
+    if live:
+        raise NotImplementedError(f"energy terms {live} are not on the accelerated path; pass 0")
+    if not any(p[n] > 0 for n in ("w_descr", "w_lap") + _ITERATIVE_TERMS):
+        raise ValueError("every energy weight is 0")                           # base_functions.py:534,639 would fail too
+    return p
+
+
+def fit_plan(p, k1):
+    """(route, L-BFGS options) of a fit with the parameters p (fit_parameters) of maps with k1 columns.
+    "closed": only w_descr / w_lap and at most CLOSED_FORM_MAX_K1 columns -- the closed form solves k2 systems of order k1 - 1 in
+    on-chip memory.  Wider quadratic fits (the reference has no cap, functional.py:352) take the reference's own scheme -- L-BFGS on
+    the two quadratic terms, on the device, float64 -- run to LBFGS_WIDE whatever `stopping` says: they replace a closed form.
+    Any other term: "iterative" with the rule `stopping` names at every width, LBFGS_OPTIONS ("tight") or SciPy's defaults (None)."""
+    if any(p[n] > 0 for n in _ITERATIVE_TERMS):
+        return "iterative", (LBFGS_OPTIONS if p["stopping"] == "tight" else None)
+    if k1 > CLOSED_FORM_MAX_K1:
+        return "iterative", LBFGS_WIDE
+    return "closed", None
+
+
 def _orient_row_scale(mesh):
     """mass / vertex_areas, the row scale that turns Phi into the left factor of compute_orientation_op's operators (pinv = Phi^T A, rows
     divided by vertex_areas); None where it is 1 everywhere (TriMesh: the row sums of a lumped A are its diagonal), i.e. the "mass" form"""
@@ -34,6 +77,95 @@ def _orient_row_scale(mesh):
         raise NotImplementedError("the device route of the orientation operators takes a lumped (diagonal) mass matrix; use the host route")
     va = np.asarray(mesh.vertex_areas, dtype=np.float64)
     return None if np.array_equal(mass, va) else mass / va
+
+
+def _orientation_ops_device(eng, models, Phis, Fs, area):
+    """the orientation operators of a group of models of one size, both meshes, as device tensors (nb, D, k1, k1), (nb, D, k2, k2), never
+    reversed (MatchEngine.orientation_ops on the stacked meshes; face counts may differ inside a group: padded, n_faces), and whether
+    `area` made a difference.  Phis: the stacked bases in the meshes' own precision, Fs: the stacked descriptors as the fit stages them
+    (fp16 when both sets are fp16, else fp32).  area "vertex": rows divided by vertex_areas, "mass": by diag(A) -- lumped masses ARE the
+    vertex areas, the two forms are then the same operators."""
+    if area not in ("vertex", "mass"):
+        raise ValueError(f'area must be "vertex" or "mass", not {area!r}')
+    out, scaled = [], False
+    for side, (Phi, F) in enumerate(zip(Phis, Fs)):
+        meshes = [(m.mesh1, m.mesh2)[side] for m in models]
+        k = (models[0].k1, models[0].k2)[side]
+        verts = np.stack([np.asarray(m.vertlist, dtype=np.float64) for m in meshes])
+        nf = np.array([m.facelist.shape[0] for m in meshes], dtype=np.int32)
+        faces = np.zeros((len(meshes), int(nf.max()), 3), dtype=np.int32)
+        for q, m in enumerate(meshes):
+            faces[q, :nf[q]] = m.facelist
+        rs = [_orient_row_scale(m) for m in meshes]
+        scale = None
+        if any(r is not None for r in rs):
+            scaled = True
+            if area == "vertex":
+                scale = np.stack([np.ones(m.n_vertices) if r is None else r for m, r in zip(meshes, rs)])
+        out.append(eng.orientation_ops(verts, faces, Phi, F, k=k, row_scale=scale, n_faces=nf))
+    return tuple(out), scaled
+
+
+def _orientation_ops(eng, models, p, own, dev):
+    """both operator sets of functional.py:432-456 for a group, each a pair (nb, D, k, k): the rescaling operators (rows divided by
+    vertex_areas, the second reversed on request: compute_orientation_op) and those the optimisation runs with (energy_func_std rebuilds
+    them itself, base_functions.py:567-597: rows divided by diag(A), never reversed) -- both restated as they are."""
+    if p["orient_route"] == "host":
+        st = lambda ops, side: np.stack([np.stack([o[side] for o in ops_q]) for ops_q in ops])
+        resc = [m.compute_orientation_op(reversing=p["orient_reversing"]) for m in models]
+        fit = [m.compute_orientation_op(reversing=False, area="mass") for m in models]
+        return (st(resc, 0), st(resc, 1)), (st(fit, 0), st(fit, 1))
+    Fs = (dev["F1"], dev["F2"])
+    (r1, r2), scaled = _orientation_ops_device(eng, models, own[:2], Fs, "vertex")
+    fit = _orientation_ops_device(eng, models, own[:2], Fs, "mass")[0] if scaled else (r1, r2)
+    return (r1, -r2 if p["orient_reversing"] else r2), fit
+
+
+def fit_models(eng, models, p, dev, own, report=None):
+    """The fit of a group of models of one size (FunctionalMapping.fit passes [self], compute_surface_map_batch its size groups): from the
+    staged inputs to C (nb, k2, k1) float64, stored on the models with fit_result, eta and w_orient_rescaled.
+    p: fit_parameters(...); dev: the fit's device inputs, stacked (Phi1, Phi2, a1, a2 fp32 like the reference's fit, functional.py:412-413;
+    lam1, lam2 float64; F1, F2 fp16 | fp32); own = (Phi1, Phi2, a1, a2): stacked bases and masses in the meshes' own precision (the
+    pinned entry of the closed form, the device route of the orientation operators); report(eng, dev, weights, x, orient_ops, where):
+    called at the start point and at the solution of an iterative fit."""
+    import types
+    nb = len(models)
+    route, lbfgs_options = fit_plan(p, dev["Phi1"].shape[2])
+    res = None
+    if route == "closed":
+        A = eng.project(dev["Phi1"], dev["a1"], dev["F1"])
+        B = eng.project(dev["Phi2"], dev["a2"], dev["F2"])
+        # pinned entry from the float64 spectrum and masses (get_x0 is float64 host code in the reference, :654-658)
+        c00 = eng.c00(*own)
+        C = eng.fmap_solve(A, B, dev["lam1"], dev["lam2"], c00, p["w_descr"], p["w_lap"], check=True).cpu().numpy()
+    else:
+        weights = {n: p[n] for n in ("w_descr", "w_lap") + _ITERATIVE_TERMS}
+        x0 = np.stack([m.get_x0(optinit=p["optinit"]) for m in models])
+        orient_ops = None
+        if p["w_orient"] > 0:
+            # functional.py:432-456: every pair's weight rescaled by (energy of the other terms at x0) / (orientation energy at x0)
+            resc_ops, orient_ops = _orientation_ops(eng, models, p, own, dev)
+            e_native = eng.fit_energy(dev, dict(weights, w_orient=0.0), x0)
+            e_orient = eng.fit_energy(dev, dict(w_orient=1.0), x0, orient_ops=resc_ops)
+            w_orient = [p["w_orient"] * float(e_native[q]) / float(e_orient[q]) for q in range(nb)]
+            for q, m in enumerate(models):
+                m.w_orient_rescaled = w_orient[q]
+            weights["w_orient"] = np.asarray(w_orient, dtype=np.float64)
+        if report is not None:
+            report(eng, dev, weights, x0, orient_ops, "x0")
+        C, res = eng.fit_general(dev, weights, x0, maxiter=p["maxiter"], lbfgs_options=lbfgs_options, driver=p["driver"], orient_ops=orient_ops)
+        C = np.asarray(C, dtype=np.float64)
+        if report is not None:
+            report(eng, dev, weights, C, orient_ops, "solution")
+    for q, m in enumerate(models):
+        m.FM = C[q]
+        m.eta = np.ones(m.mesh2.eigenvectors.shape[0])                         # functional.py:483
+        if res is not None:
+            # (a group's result holds one entry per pair: every model keeps its own slice.  A group of one keeps the result as it is:
+            #  with driver="scipy" -- one pair per call -- it is SciPy's OptimizeResult, which has no per-pair axis to slice)
+            m.fit_result = res if nb == 1 else types.SimpleNamespace(nit=res.nit[q:q + 1], nfev=res.nfev[q:q + 1], fun=res.fun[q:q + 1],
+                                                                     status=res.status[q:q + 1], message=res.message[q:q + 1])
+    return C, res
 
 
 class FunctionalMapping:
@@ -114,10 +246,12 @@ class FunctionalMapping:
 
     # ---------------------------------------------------------------- preprocess (functional.py:264-350)
     def preprocess(self, n_ev=(50, 50), n_descr=100, descr_type='WKS', landmarks=None, subsample_step=1, k_process=None,
-                   verbose=False, descr1=None, descr2=None, signature_route="host"):
+                   verbose=False, descr1=None, descr2=None, signature_route="host", robust_backend=None):
         """signature_route (not in the reference): where descr_type 'HKS' / 'WKS' is evaluated.  "host" (default): the NumPy mirror
         of the reference, pyFM/signatures.py; "device": MatchEngine.signatures, the [plain | landmark] blocks of both meshes in one
-        call, downloaded as NumPy float64 (equal to the host's up to the summation order and the device's exp)."""
+        call, downloaded as NumPy float64 (equal to the host's up to the summation order and the device's exp).
+        robust_backend (not in the reference): 'wheel' | 'restated' for the Laplacians of this call (TriMesh.process), None: the
+        process default; meshes that bring their own `process` receive it only when the call names one."""
         if signature_route not in ("host", "device"):
             raise ValueError(f'signature_route must be "host" or "device", not {signature_route!r}')
         self.k1, self.k2 = n_ev
@@ -127,10 +261,11 @@ class FunctionalMapping:
         # (functional.py:300-301: mesh1.process, mesh2.process; here the two eigensolves share one batched call)
         ks = [max(self.k1, k_process), max(self.k2, k_process)]
         if all(hasattr(m, "_assemble_laplacian") for m in (self.mesh1, self.mesh2)):
-            type(self.mesh1).process_many([self.mesh1, self.mesh2], ks, robust=True, verbose=verbose)
+            type(self.mesh1).process_many([self.mesh1, self.mesh2], ks, robust=True, verbose=verbose, robust_backend=robust_backend)
         else:                                                                    # (duck-typed meshes bring their own process)
-            self.mesh1.process(ks[0], verbose=verbose, robust=True, intrinsic=False)
-            self.mesh2.process(ks[1], verbose=verbose, robust=True, intrinsic=False)
+            own = {} if robust_backend is None else {"robust_backend": robust_backend}
+            self.mesh1.process(ks[0], verbose=verbose, robust=True, intrinsic=False, **own)
+            self.mesh2.process(ks[1], verbose=verbose, robust=True, intrinsic=False, **own)
         if use_lm:
             lmks1, lmks2 = self._get_lmks(landmarks)
         if descr1 is not None and descr2 is not None:
@@ -179,7 +314,8 @@ class FunctionalMapping:
             orient_reversing=False, optinit='zeros', verbose=False, maxiter=1000000, device=None, stopping="reference", driver="device",
             orient_route="host"):
         """reference functional.py:352-487.  With only w_descr / w_lap > 0 the minimiser (what the reference's L-BFGS-B
-        converges to, first column pinned) is obtained in closed form on the GPU.  With any of
+        converges to, first column pinned) is obtained in closed form on the GPU for maps up to
+        CLOSED_FORM_MAX_K1 columns; wider maps run L-BFGS on the two terms to LBFGS_WIDE, whatever `stopping` says.  With any of
         w_dcomm, w_orient, w_area, w_conformal, w_p2p, w_stochastic, w_ent, w_range01, w_sumto1 > 0 the reference's own scheme
         runs: limited-memory BFGS with L-BFGS-B's line search and stopping tests (scipy.optimize.minimize, :477) from
         get_x0(optinit), on the device, energy and gradient in float64 (maps up to 32 x 32 with the notebook's kind of terms:
@@ -187,101 +323,44 @@ class FunctionalMapping:
         Only the area-difference, Mumford-Shah and eta-entropy terms are not on the path (NotImplementedError).
         stopping = "reference" (default): SciPy's default rule, i.e. what the reference's call runs with (ftol 2.2e-9, gtol 1e-5):
         the fit ends where the reference's ends, a few 1e-4 short of the minimiser, and the drop-in agrees best with the
-        reference's own outputs (INTEGRATION.md has the per-slot table); "tight": ftol 1e-12, the float64 minimiser to 1e-5.
+        reference's own outputs (INTEGRATION.md has the per-slot table); "tight": ftol 1e-12, the float64 minimiser to 1e-5.  The
+        rule holds at every width of the map (fit_plan).  The parameters are checked by fit_parameters, the fit itself is
+        fit_models -- both shared with compute_surface_map_batch.
         orient_route (not in the reference; read when w_orient > 0): "host" (default) builds the orientation operators with
         compute_orientation_op's sparse products per descriptor, as the reference does; "device" builds both operator sets
         (rescaling and optimisation) with MatchEngine.orientation_ops and keeps them on the device until the fit has read them.
         The device route reads the descriptors the fit itself reads (fp16 / fp32): for float64 descriptors that are not fp32
         numbers its operators differ from the host route's at 1e-7 relative."""
+        p = fit_parameters(dict(
+            w_descr=w_descr, w_lap=w_lap, w_dcomm=w_dcomm, w_orient=w_orient, w_area=w_area, w_conformal=w_conformal, w_p2p=w_p2p,
+            w_stochastic=w_stochastic, w_ent=w_ent, w_range01=w_range01, w_sumto1=w_sumto1, w_area_difference=w_area_difference,
+            w_mumford_shah=w_mumford_shah, mumford_shah_var=mumford_shah_var, w_eta_entropy=w_eta_entropy, orient_reversing=orient_reversing,
+            optinit=optinit, verbose=verbose, maxiter=maxiter, device=device, stopping=stopping, driver=driver, orient_route=orient_route))
         from ..engine import default_engine
-        if orient_route not in ("host", "device"):
-            raise ValueError(f'orient_route must be "host" or "device", not {orient_route!r}')
-        if optinit not in ['random', 'identity', 'zeros']:
-            raise ValueError(f"optinit arg should be 'random', 'identity' or 'zeros', not {optinit}")
+        from .spectral.convert import _real_dtype
+        import torch
         if self.optimizer not in _OPTIMIZERS:
             raise ValueError(f"Unknown solver {self.optimizer}")
         if self.partial:
             raise NotImplementedError()                                        # functional.py:480
-        off_path = dict(w_area_difference=w_area_difference, w_mumford_shah=w_mumford_shah, w_eta_entropy=w_eta_entropy)
-        live = [n for n, v in off_path.items() if v > 0]
-        if live:
-            raise NotImplementedError(f"energy terms {live} are not on the accelerated path; pass 0")
-        general = dict(w_dcomm=w_dcomm, w_p2p=w_p2p, w_stochastic=w_stochastic, w_ent=w_ent, w_range01=w_range01, w_sumto1=w_sumto1,
-                       w_orient=w_orient, w_area=w_area, w_conformal=w_conformal)
-        iterative = any(v > 0 for v in general.values())
-        if not (w_descr > 0 or w_lap > 0 or iterative):
-            raise ValueError("every energy weight is 0")                       # base_functions.py:534,639 would fail too
-        # The closed form solves k2 systems of order k1 - 1 in on-chip memory: maps up to 200 columns.  Wider maps (the reference has no
-        # cap, functional.py:352) take the reference's own scheme instead -- L-BFGS on the two quadratic terms, on the device, float64,
-        # run to ftol 1e-12 (the float64 minimiser to 1e-5) unless the caller asked for the reference's stopping rule explicitly.
         if not self.preprocessed:
             self.preprocess()
-        wide = (not iterative) and self.mesh1.eigenvectors.shape[1] > CLOSED_FORM_MAX_K1
         eng = default_engine()
         m1, m2 = self.mesh1, self.mesh2
         # like the reference (functional.py:412-413) fit uses every stored eigenvector column
-        Phi1 = np.ascontiguousarray(m1.eigenvectors, dtype=np.float32)[None]
-        Phi2 = np.ascontiguousarray(m2.eigenvectors, dtype=np.float32)[None]
-        a1 = np.ascontiguousarray(m1.A.diagonal(), dtype=np.float32)[None]
-        a2 = np.ascontiguousarray(m2.A.diagonal(), dtype=np.float32)[None]
         d1, d2 = np.asarray(self.descr1), np.asarray(self.descr2)
         fdt = np.float16 if (d1.dtype == np.float16 and d2.dtype == np.float16) else np.float32
-        batch = {"Phi1": Phi1, "Phi2": Phi2, "a1": a1, "a2": a2,
-                 "lam1": np.asarray(m1.eigenvalues, dtype=np.float64)[None], "lam2": np.asarray(m2.eigenvalues, dtype=np.float64)[None],
-                 "F1": np.ascontiguousarray(d1, dtype=fdt)[None], "F2": np.ascontiguousarray(d2, dtype=fdt)[None]}
-        dev = {n: eng._dev(v, {np.float16: __import__("torch").float16, np.float32: __import__("torch").float32,
-                               np.float64: __import__("torch").float64}[v.dtype.type], n) for n, v in batch.items()}
-        if iterative or wide:
-            weights = dict(w_descr=w_descr, w_lap=w_lap, **general)
-            if wide:
-                stopping = "tight"
-            if stopping not in ("tight", "reference"):
-                raise ValueError("stopping must be 'tight' or 'reference'")
-            x0 = self.get_x0(optinit=optinit)
-            orient_ops = None
-            if w_orient > 0:
-                # functional.py:432-456: the orientation operators, and the weight rescaled by (energy of the other terms at x0) /
-                # (orientation energy at x0).  The reference rescales with the NumPy operators of compute_orientation_op
-                # (reversing honoured there) and then OPTIMISES with the operators energy_func_std rebuilds itself
-                # (base_functions.py:567-597: rows divided by diag(A), never reversed) -- both restated as they are.
-                if orient_route == "device":
-                    r1, r2 = self._orientation_ops_device("vertex")
-                    o1, o2 = r1, (-r2 if orient_reversing else r2)
-                else:
-                    resc = self.compute_orientation_op(reversing=orient_reversing)
-                    o1 = np.stack([a for a, _ in resc])[None]
-                    o2 = np.stack([b for _, b in resc])[None]
-                w_native = dict(weights, w_orient=0.0)
-                e_native = eng.fit_energy(dev, w_native, x0[None])
-                e_orient = eng.fit_energy(dev, dict(w_orient=1.0), x0[None], orient_ops=(o1, o2))
-                w_orient = w_orient * float(e_native[0]) / float(e_orient[0])
-                weights["w_orient"] = w_orient
-                self.w_orient_rescaled = w_orient
-                if orient_route == "device":
-                    # (lumped masses ARE the vertex areas -- A diagonal: the two forms are the same operators, one call serves both)
-                    same = all(_orient_row_scale(m) is None for m in (m1, m2))
-                    orient_ops = (r1, r2) if same else self._orientation_ops_device("mass")
-                else:
-                    fit_ops = self.compute_orientation_op(reversing=False, area="mass")
-                    orient_ops = (np.stack([a for a, _ in fit_ops])[None], np.stack([b for _, b in fit_ops])[None])
-            self._verbose_terms(eng, dev, weights, x0, orient_ops, "x0")
-            C, res = eng.fit_general(dev, weights, x0[None], maxiter=maxiter,
-                                     lbfgs_options=(LBFGS_WIDE if wide else LBFGS_OPTIONS) if stopping == "tight" else None, driver=driver,
-                                     orient_ops=orient_ops)
-            self.FM = np.asarray(C[0], dtype=np.float64)
-            self.fit_result = res
-            self._verbose_terms(eng, dev, weights, self.FM, orient_ops, "solution")
-            if verbose:
-                print(f"\tTask funcall : {res.nfev}, nit : {res.nit}, warnflag : {res.message}")
-        else:
-            A = eng.project(dev["Phi1"], dev["a1"], dev["F1"])
-            B = eng.project(dev["Phi2"], dev["a2"], dev["F2"])
-            # pinned entry from the float64 spectrum and masses (get_x0 is float64 host code in the reference, :654-658)
-            c00 = eng.c00(np.ascontiguousarray(m1.eigenvectors)[None], np.ascontiguousarray(m2.eigenvectors)[None],
-                        np.ascontiguousarray(m1.A.diagonal())[None], np.ascontiguousarray(m2.A.diagonal())[None])
-            C = eng.fmap_solve(A, B, dev["lam1"], dev["lam2"], c00, w_descr, w_lap, check=True)
-            self.FM = C[0].cpu().numpy()
-        self.eta = np.ones(m2.eigenvectors.shape[0])                           # functional.py:483
+        one = lambda x, dt: np.ascontiguousarray(x, dtype=dt)[None]
+        a1, a2 = m1.A.diagonal(), m2.A.diagonal()
+        batch = {"Phi1": one(m1.eigenvectors, np.float32), "Phi2": one(m2.eigenvectors, np.float32), "a1": one(a1, np.float32), "a2": one(a2, np.float32),
+                 "lam1": one(m1.eigenvalues, np.float64), "lam2": one(m2.eigenvalues, np.float64), "F1": one(d1, fdt), "F2": one(d2, fdt)}
+        tdt = {np.float16: torch.float16, np.float32: torch.float32, np.float64: torch.float64}
+        dev = {n: eng._dev(v, tdt[v.dtype.type], n) for n, v in batch.items()}
+        rdt = _real_dtype(m1.eigenvectors, m2.eigenvectors)
+        own = (one(m1.eigenvectors, rdt), one(m2.eigenvectors, rdt), one(a1, None), one(a2, None))
+        _, res = fit_models(eng, [self], p, dev, own, report=self._verbose_terms)
+        if verbose and res is not None:
+            print(f"\tTask funcall : {res.nfev}, nit : {res.nit}, warnflag : {res.message}")
         self._dev = dev
 
     # the reference's per-term printout (base_functions.py:27-29, 538-636: `VERBOSE` in the environment prints every live term's
@@ -293,14 +372,15 @@ class FunctionalMapping:
                        ("w_sumto1", "sumto1 loss:"))
 
     def _verbose_terms(self, eng, dev, weights, x, orient_ops, where):
+        """x (1, k2, k1); weights as fit_general takes them (w_orient: one weight per pair)"""
         import os
         if not os.environ.get("VERBOSE", False):
             return
         print(f"energy terms at the {where}:")
         for name, label in self._VERBOSE_LABELS:
             w = weights.get(name, 0)
-            if w > 0:
-                e = eng.fit_energy(dev, {name: w}, np.asarray(x)[None], orient_ops=orient_ops if name == "w_orient" else None)
+            if np.any(np.asarray(w) > 0):
+                e = eng.fit_energy(dev, {name: w}, x, orient_ops=orient_ops if name == "w_orient" else None)
                 print(label, float(e[0]))
 
     def compute_orientation_op(self, reversing=False, normalize=False, area="vertex", route="host"):
@@ -316,7 +396,15 @@ class FunctionalMapping:
         if route == "device":
             if normalize:
                 raise NotImplementedError('compute_orientation_op(normalize=True) is not on the device route; use route="host"')
-            o1, o2 = (o[0].cpu().numpy() for o in self._orientation_ops_device(area))
+            from ..engine import default_engine
+            from .spectral.convert import _real_dtype
+            d1, d2 = np.asarray(self.descr1), np.asarray(self.descr2)
+            fdt = np.float16 if (d1.dtype == np.float16 and d2.dtype == np.float16) else np.float32      # (the dtype fit() stages)
+            rdt = _real_dtype(self.mesh1.eigenvectors, self.mesh2.eigenvectors)
+            one = lambda x, dt: np.ascontiguousarray(x, dtype=dt)[None]
+            ops, _ = _orientation_ops_device(default_engine(), [self], (one(self.mesh1.eigenvectors, rdt), one(self.mesh2.eigenvectors, rdt)),
+                                             (one(d1, fdt), one(d2, fdt)), area)
+            o1, o2 = (o[0].cpu().numpy() for o in ops)
             return [(a, -b if reversing else b) for a, b in zip(o1, o2)]
         out = []
         sides = []
@@ -330,24 +418,6 @@ class FunctionalMapping:
         for a, b in zip(*sides):
             out.append((a, -b if reversing else b))
         return out
-
-    def _orientation_ops_device(self, area):
-        """the orientation operators of both meshes as device tensors (1, D, k1, k1), (1, D, k2, k2), never reversed"""
-        from ..engine import default_engine
-        from .spectral.convert import _real_dtype
-        if area not in ("vertex", "mass"):
-            raise ValueError(f'area must be "vertex" or "mass", not {area!r}')
-        eng = default_engine()
-        d1, d2 = np.asarray(self.descr1), np.asarray(self.descr2)
-        fdt = np.float16 if (d1.dtype == np.float16 and d2.dtype == np.float16) else np.float32      # (the dtype fit() stages)
-        rdt = _real_dtype(self.mesh1.eigenvectors, self.mesh2.eigenvectors)
-        out = []
-        for mesh, descr, k in ((self.mesh1, d1, self.k1), (self.mesh2, d2, self.k2)):
-            rs = _orient_row_scale(mesh) if area == "vertex" else None
-            out.append(eng.orientation_ops(np.asarray(mesh.vertlist, dtype=np.float64)[None], np.asarray(mesh.facelist)[None],
-                                           np.ascontiguousarray(np.asarray(mesh.eigenvectors)[:, :k], dtype=rdt)[None],
-                                           np.ascontiguousarray(descr, dtype=fdt)[None], row_scale=None if rs is None else rs[None]))
-        return tuple(out)
 
     def get_x0(self, optinit="zeros"):
         """functional.py:629-660"""

@@ -32,10 +32,16 @@ import scipy.sparse as sparse
 _ROBUST_BACKEND = [os.environ.get("DENSEMATCHER_AMD_ROBUST_LAPLACIAN", "wheel")]
 
 
-def set_robust_backend(name):
-    if name not in ("wheel", "restated"):
+def check_robust_backend(name, allow_none=True):
+    """raises ValueError unless `name` is a backend (or None, a call that names none); returns it"""
+    if not (name in ("wheel", "restated") or (name is None and allow_none)):
         raise ValueError("robust backend must be 'wheel' or 'restated'")
-    _ROBUST_BACKEND[0] = name
+    return name
+
+
+def set_robust_backend(name):
+    """the process default (what a call runs that names no backend of its own)"""
+    _ROBUST_BACKEND[0] = check_robust_backend(name, allow_none=False)
 
 
 def robust_backend():

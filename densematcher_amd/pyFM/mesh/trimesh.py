@@ -222,10 +222,11 @@ class TriMesh:
         return np.asarray(self.A.diagonal())
 
     @staticmethod
-    def _assemble_many(meshes, robust=False):
+    def _assemble_many(meshes, robust=False, robust_backend=None):
         """Stiffness rows and lumped masses of several meshes.  Returns the dict MatchEngine.laplacian_ell produced (the operands of
         dm_eigenbasis, on the device, meshes padded to the largest) -- or None when the robust_laplacian wheel assembled the
-        matrices on the host (the caller then hands W, A to the eigensolver as SciPy matrices)."""
+        matrices on the host (the caller then hands W, A to the eigensolver as SciPy matrices).
+        robust_backend: 'wheel' | 'restated' for this call, None: the process default (laplacian.robust_backend())."""
         from ...engine import default_engine
         from . import laplacian as _lap
         for mesh in meshes:
@@ -246,7 +247,8 @@ class TriMesh:
                     mesh.A = sparse.diags(mass).tocsr()
                     mesh._L = None
                 return None
-            if _lap.robust_backend() != "restated":
+            backend = _lap.robust_backend() if robust_backend is None else _lap.check_robust_backend(robust_backend)
+            if backend != "restated":
                 raise ImportError(
                     "process(robust=True) -- what FunctionalMapping.preprocess and compute_surface_map always ask for -- needs the "
                     "`robust_laplacian` package (what the reference calls, pyFM/mesh/trimesh.py:465-470), which is not installed.  This "
@@ -293,9 +295,9 @@ class TriMesh:
         return (self.eigenvectors is not None) and (self.eigenvalues is not None) and (len(self.eigenvalues) >= k)
 
     # ------------------------------------------------------------- spectrum (host side input of the path)
-    def laplacian_spectrum(self, k, intrinsic=False, return_spectrum=True, robust=False, verbose=False):
+    def laplacian_spectrum(self, k, intrinsic=False, return_spectrum=True, robust=False, verbose=False, robust_backend=None):
         """trimesh.py:440-496 -> laplacian.py:143-182.  W, A assembled on the device; the k smallest eigenpairs on the GPU."""
-        ell = TriMesh._assemble_many([self], robust)
+        ell = TriMesh._assemble_many([self], robust, robust_backend)
         if k > 0:
             kk = self._n_eigs(k)
             from ...engine import default_engine
@@ -307,26 +309,29 @@ class TriMesh:
             if return_spectrum:
                 return self.eigenvalues, self.eigenvectors
 
-    def process(self, k=200, skip_normals=True, intrinsic=False, robust=False, verbose=False):
-        """trimesh.py:498-531: reuse a stored spectrum when it is large enough, else compute it."""
+    def process(self, k=200, skip_normals=True, intrinsic=False, robust=False, verbose=False, robust_backend=None):
+        """trimesh.py:498-531: reuse a stored spectrum when it is large enough, else compute it.
+        robust_backend (not in the reference): as for _assemble_many."""
         if self._has_spectrum(k):
             self.eigenvectors = self.eigenvectors[:, :k]
             self.eigenvalues = self.eigenvalues[:k]
         else:
-            self.laplacian_spectrum(k, return_spectrum=False, intrinsic=intrinsic, robust=robust, verbose=verbose)
+            self.laplacian_spectrum(k, return_spectrum=False, intrinsic=intrinsic, robust=robust, verbose=verbose, robust_backend=robust_backend)
         return self
 
     @staticmethod
-    def process_many(meshes, ks, robust=False, verbose=False):
+    def process_many(meshes, ks, robust=False, verbose=False, robust_backend=None):
         """mesh.process(k) for several meshes (FunctionalMapping.preprocess: functional.py:300-301 processes its two meshes one
         after the other).  One device assembly and ONE batched eigensolve for the meshes that still need a spectrum (the
         eigensolver is a chain of small launches whose duration does not depend on how many meshes ride along; the smaller meshes
-        are padded); each keeps its own k pairs."""
+        are padded); each keeps its own k pairs.  robust_backend: as for _assemble_many; a mesh's own `process` receives it only when
+        the call names one."""
+        own = {} if robust_backend is None else {"robust_backend": robust_backend}
         todo = []
         for mesh, k in zip(meshes, ks):
             # (a subclass or a patched `process` -- a caller that supplies its own spectra -- keeps the say)
             if mesh._has_spectrum(k) or k <= 0 or type(mesh).process is not _TRIMESH_PROCESS:
-                mesh.process(k, robust=robust, verbose=verbose)
+                mesh.process(k, robust=robust, verbose=verbose, **own)
             else:
                 todo.append((mesh, k))
         if not todo:
@@ -340,9 +345,9 @@ class TriMesh:
         # exceed it -- the meshes are solved one by one, each with its own k (small ones by the dense route)
         if len(todo) > 1 and (2 * (kk + 32) > nmin or kk > nmin - 1):
             for mesh, k in todo:
-                mesh.process(k, robust=robust, verbose=verbose)
+                mesh.process(k, robust=robust, verbose=verbose, **own)
             return meshes
-        ell = TriMesh._assemble_many([mesh for mesh, _ in todo], robust)
+        ell = TriMesh._assemble_many([mesh for mesh, _ in todo], robust, robust_backend)
         if ell is None:
             lam, phi, resid, _ = eng.eigenbasis([mesh.W for mesh, _ in todo], [np.asarray(mesh.A.diagonal()) for mesh, _ in todo], kk, tol=1e-10)
         else:

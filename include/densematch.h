@@ -106,10 +106,6 @@ size_t dm_workspace_bytes(const dm_ctx* ctx);
  *   "basis_stats"   1 | 0   dm_fm_to_p2p: keep the maximum of |Phi2| per basis tensor between calls (a checked hint: the target operand's
  *                           fp16 rows are then written while the basis streams through the second embedding) | every call takes its own
  *                           pass over the basis.  Same results.
- *   "fit_f32"       0 | 1   dm_fmap_fit_fused: the element loop over the N2 x N1 entries of the mapped indicator in float64 | in fp32,
- *                           the precision the reference evaluates these terms in (pyFM/functional.py:379-383).  The ONE option whose two
- *                           settings differ in the result: energy / gradient within 1e-6 relative, the fitted map within 3e-6 under
- *                           SciPy's stopping rule.  The Python layer chooses it from the stopping rule (engine.py: _fit_fused).
  *   "fit_mfma"      1 | 0   the fp32 element loop for maps up to 16 x 16: the two 16-deep products of an entry (the entry itself and the
  *                           back-product of its derivative) on v_mfma_f32_16x16x4_f32, the element-wise terms alone on the vector ALU | both
  *                           on the packed vector FMA.  Different summation orders of the same fp32 arithmetic: both within 1e-7 (energy) /
@@ -273,6 +269,10 @@ int dm_fmap_fit_steps(dm_ctx* ctx, int nsteps, int B, int N1, int N2, int k1, in
  *   x0 (B,k2,k1) start (first column = the pinned one); x_out (B,k2,k1), f_out (B), info_out (B,4) as dm_lbfgs_result;
  *   evaluations_out (host, nullable): launches issued.
  *   maxfun <= 0: ONE evaluation at x0, no optimiser: f_out (B) energy, grad_out (B,k2,k1) gradient (x_out / info_out unused).
+ *   element_f32 0 | 1 (both modes): the element loop over the N2 x N1 entries of the mapped indicator in float64 | in fp32, the
+ *                         precision the reference evaluates these terms in (pyFM/functional.py:379-383).  The two differ in the result:
+ *                         energy / gradient within 1e-6 relative, the fitted map within 3e-6 under SciPy's stopping rule.  The Python
+ *                         layer chooses it from the stopping rule (engine.py: _fit_fused).
  *   dm_fmap_fit_fused takes no operator lists, so it has no commutativity term: weights[2] (w_dcomm) must be 0, DM_EINVAL otherwise
  *   (a fit with operators goes through dm_fmap_fit_steps; dm_fmap_fit_fused_ok(..., n_ops > 0) says so). */
 int dm_fmap_fit_fused_ok(int k1, int k2, const double* weights /*host, 10*/, int n_ops);
@@ -280,7 +280,7 @@ int dm_fmap_fit_fused(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D,
                       const float* Phi1, int ld1, const float* Phi2, int ld2, const float* mass1,
                       const float* A, const float* Bm, const double* lam1, const double* lam2,
                       const double* weights /*host, 10*/, int m, const double* x0,
-                      double ftol, double pgtol, int maxiter, int maxfun, int maxls,
+                      double ftol, double pgtol, int maxiter, int maxfun, int maxls, int element_f32,
                       double* x_out, double* f_out, int32_t* info_out, double* grad_out /*nullable*/, int* evaluations_out /*host, nullable*/);
 
 /* ops[b][d] = Phi[b][:, :k]^T diag(mass[b] * F[b][:, d]) Phi[b][:, :k]   (B, D, k, k) fp64: the multiplication operator

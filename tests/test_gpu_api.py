@@ -859,6 +859,21 @@ def test_energy_keep_gram_option():
                                          e1[b].cpu().numpy(), e2[b].cpu().numpy(), a1[b].cpu().numpy(), wm)
         assert abs(float(plain[0][0][b]) - Eo) <= 1e-11 * abs(Eo)
         assert np.abs(plain[0][1][b].cpu().numpy() - Go).max() <= 1e-11 * np.abs(Go).max()
+    # the L-BFGS driver sets the option for its own evaluations and hands it back as it found it: a caller's 1 stays 1 (and 0 stays 0)
+    a2 = torch.as_tensor((rng.uniform(0.5, 1.5, (B, N2)) / N2).astype(np.float32)).to(dev)
+    batch = {"Phi1": e1, "Phi2": e2, "a1": a1, "a2": a2, "lam1": lam1, "lam2": lam2,
+             "F1": torch.as_tensor(rng.standard_normal((B, N1, D)).astype(np.float32)).to(dev),
+             "F2": torch.as_tensor(rng.standard_normal((B, N2, D)).astype(np.float32)).to(dev)}
+    x0 = np.zeros((B, k2, k1))
+    x0[:, 0, 0] = 1.0
+    for value in (1, 0):
+        eng.set_option("energy_keep_gram", value)
+        try:
+            _, res = eng.fit_general(batch, wm, x0, lbfgs_options={"maxfun": 8}, fused=False)
+            assert not hasattr(res, "path")                  # (the driver that sets the option, not the fused fit)
+            assert eng.get_option("energy_keep_gram") == value
+        finally:
+            eng.set_option("energy_keep_gram", 0)
 
 
 def test_assignment_from_the_indicator_factors(fx_cfg1, monkeypatch):

@@ -212,10 +212,15 @@ def test_fused_fit_matrix_form_same_iterations_batch_invariant(fx_cfg1):
 def test_fused_fit_precision_follows_the_stopping_rule(fx_cfg1):
     """SciPy's stopping rule (the reference's call, the default) runs the element loop in fp32 like the reference: the same iterations as
     the float64 loop, the map within 1e-4 of it (measured 3e-6), bit-identical in batches of 1, 3 and 140; a tighter rule (ftol 1e-12 is
-    below the fp32 noise floor of the energy) keeps float64"""
+    below the fp32 noise floor of the energy) keeps float64.  The precision is an argument of the library call: there is no "fit_f32"
+    option any more, and a fused fit leaves every option as it found it"""
     from densematcher_amd.engine import default_engine
     from densematcher_amd.pyFM.functional import LBFGS_OPTIONS
     eng = default_engine()
+    with pytest.raises(ValueError):
+        eng.set_option("fit_f32", 1)
+    assert "fit_f32" not in eng.OPTION_DEFAULTS
+    options = {n: eng.get_option(n) for n in eng.OPTION_DEFAULTS}
     fx = fx_cfg1
     k = 15
     x0 = orc.get_x0(k, k, float(fx["Phi1"][0, 0]), float(fx["Phi2"][0, 0]), float(fx["a1"].astype(np.float64).sum()),
@@ -237,3 +242,4 @@ def test_fused_fit_precision_follows_the_stopping_rule(fx_cfg1):
         assert np.array_equal(Cb[b], C3[b % 3]), b
     Ct, rt = eng.fit_general({n: v[:1] for n, v in b3.items()}, NOTEBOOK_W, x0[None], lbfgs_options=dict(LBFGS_OPTIONS))
     assert rt.element_loop == "f64"
+    assert {n: eng.get_option(n) for n in eng.OPTION_DEFAULTS} == options

@@ -31,6 +31,7 @@ import torch  # noqa: E402
 from densematcher_amd import synth  # noqa: E402
 from densematcher_amd.engine import default_engine  # noqa: E402
 from densematcher_amd.pyFM import FunctionalMapping, TriMesh  # noqa: E402
+from densematcher_amd.pyFM.functional import _orientation_ops_device  # noqa: E402
 
 
 def timed(fn, repeats, warmup=1):
@@ -92,7 +93,7 @@ def main():
                 return model.compute_orientation_op(), model.compute_orientation_op(area="mass")
 
             def device():
-                return model._orientation_ops_device("vertex")
+                return _orientation_ops_device(eng, [model], [m.eigenvectors[None] for m in meshes], [f[None] for f in F], "vertex")[0]
 
             def batch():
                 return [eng.orientation_ops(v, f, P, Fd, k=k) for v, f, P, Fd in stack]
