@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void lbfgs_result_kernel(int n, int B, const d
 }
 extern "C" int dm_lbfgs_result(dm_ctx* ctx, int B, int n, int m, const void* state, double* x, double* f, int32_t* info) {
     if (!ctx) return DM_EINVAL;
-    DM_REQUIRE(ctx, B > 0 && n > 0 && m > 0, "sizes must be positive");
+    DM_REQUIRE(ctx, B > 0 && n > 0 && m > 0 && m <= 64, "sizes must be positive, m <= 64");
     DM_REQUIRE(ctx, state && x && f && info, "null pointer");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     lb_layout L = lb_carve(const_cast<void*>(state), B, n, m);

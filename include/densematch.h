@@ -240,7 +240,8 @@ int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int 
  *                     (SciPy 1e-5), maxiter, maxfun (SciPy 15000), maxls (SciPy 20).  Finished pairs keep x_trial at their result.
  *   dm_lbfgs_result   x (B,n), f (B), info (B,4) = status (0 running, 1 gradient, 2 energy decrease, 3 maxiter, 4 maxfun, 5 line
  *                     search failed), iterations, evaluations, history length
- * The host alternates dm_fmap_energy_grad and dm_lbfgs_advance and reads info every few evaluations. */
+ * The host alternates dm_fmap_energy_grad and dm_lbfgs_advance and reads info every few evaluations.
+ * All three take 1 <= m <= 64 (B, n >= 1, no null pointer) and return DM_EINVAL otherwise. */
 size_t dm_lbfgs_state_bytes(int B, int n, int m);
 int dm_lbfgs_init(dm_ctx* ctx, int B, int n, int m, const double* x0, void* state, double* x_trial);
 int dm_lbfgs_advance(dm_ctx* ctx, int B, int n, int m, void* state, const double* energy, const double* grad, double* x_trial,
