@@ -45,15 +45,16 @@ __device__ __forceinline__ f16x8 tr_frag(const _Float16* base, int row0, int col
     return r;
 }
 
-// max |mass[n] * Phi[n][c]| per pair -> power-of-two scale.  The basis is streamed as one flat float4 array (all ld
-// columns: entries beyond k can only make the scale more conservative), four loads in flight per thread.
+// max |mass[n] * Phi[n][c]| over the columns c < k of a pair -> power-of-two scale.  The basis is streamed as one flat float4
+// array, four loads in flight per thread; what lies behind column k is loaded with its row and left out of the maximum (the
+// scale belongs to the logical operand: an Inf or a 1e30 in the padding would zero or overflow every projected value).
 // (TR = float | double: a float64 basis / mass is rounded to fp32 as it is loaded -- what the reference's fit does before it
 //  projects, pyFM/functional.py:410-414 -- so both forms compute the same numbers)
 // A float64 basis is also WRITTEN BACK as fp32 by this pass (phi32 / mass32, nullable): the tile kernel re-reads every slab
 // of the basis once per descriptor tile from L2 and is bound by that traffic (87 us on fp32, 127 us straight from float64).
 template <typename TR>
 __global__ __launch_bounds__(256) void proj_absmax_kernel(const TR* __restrict__ Phi, const TR* __restrict__ mass, int N,
-                                                          int ld, float* __restrict__ amax_part, float* __restrict__ phi32,
+                                                          int ld, int k, float* __restrict__ amax_part, float* __restrict__ phi32,
                                                           float* __restrict__ mass32, int n_part, dm_c00_args<TR> cz) {
     const int b = blockIdx.y;
     if ((int)blockIdx.x >= n_part) {                          // (uniform) the extra workgroup of dm_fmap_fit: the pair's c00
@@ -64,6 +65,7 @@ __global__ __launch_bounds__(256) void proj_absmax_kernel(const TR* __restrict__
     const TR* P = Phi + (long long)b * N * ld;
     const TR* a = mass + (long long)b * N;
     const unsigned total = (unsigned)N * (unsigned)ld;           // < 2^31 per pair (checked by the caller)
+    const unsigned kk = (unsigned)k;
     float m = 0.f;
     if (sizeof(TR) == 4 && ((ld & 3) == 0) && ((((uintptr_t)Phi) & 15) == 0)) {
         const unsigned nvec = total >> 2, ld4 = (unsigned)ld >> 2;
@@ -74,16 +76,22 @@ __global__ __launch_bounds__(256) void proj_absmax_kernel(const TR* __restrict__
         for (unsigned c0 = blockIdx.x * 1024; c0 < nvec; c0 += n_part * 1024) {
             float4 v[4];
             float an[4];
+            unsigned col[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned e = c0 + u * 256 + threadIdx.x;
                 const bool ok = e < nvec;
+                const unsigned row = e / ld4;                      // 32-bit division (a 64-bit one dominated this kernel)
+                col[u] = (e - row * ld4) * 4;
                 v[u] = ok ? P4[e] : float4{0.f, 0.f, 0.f, 0.f};
-                an[u] = ok ? fabsf((float)a[e / ld4]) : 0.f;       // 32-bit division (a 64-bit one dominated this kernel)
+                an[u] = ok ? fabsf((float)a[row]) : 0.f;
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                m = fmaxf(m, an[u] * fmaxf(fmaxf(fabsf(v[u].x), fabsf(v[u].y)), fmaxf(fabsf(v[u].z), fabsf(v[u].w))));
+            for (int u = 0; u < 4; ++u) {
+                const float x = col[u] < kk ? fabsf(v[u].x) : 0.f, y = col[u] + 1 < kk ? fabsf(v[u].y) : 0.f;
+                const float z = col[u] + 2 < kk ? fabsf(v[u].z) : 0.f, w = col[u] + 3 < kk ? fabsf(v[u].w) : 0.f;
+                m = fmaxf(m, an[u] * fmaxf(fmaxf(x, y), fmaxf(z, w)));
+            }
         }
     } else if (sizeof(TR) == 8 && ((ld & 1) == 0) && ((((uintptr_t)Phi) & 15) == 0)) {
         const unsigned nvec = total >> 1, ld2 = (unsigned)ld >> 1;
@@ -91,24 +99,28 @@ __global__ __launch_bounds__(256) void proj_absmax_kernel(const TR* __restrict__
         for (unsigned c0 = blockIdx.x * 1024; c0 < nvec; c0 += n_part * 1024) {
             f64x2 v[4];
             float an[4];
+            unsigned col[4];
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const unsigned e = c0 + u * 256 + threadIdx.x;
                 const bool ok = e < nvec;
+                const unsigned row = e / ld2;
+                col[u] = (e - row * ld2) * 2;
                 v[u] = ok ? P2[e] : f64x2{0.0, 0.0};
-                an[u] = ok ? fabsf((float)a[e / ld2]) : 0.f;
+                an[u] = ok ? fabsf((float)a[row]) : 0.f;
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const float x0 = (float)v[u][0], x1 = (float)v[u][1];
-                m = fmaxf(m, an[u] * fmaxf(fabsf(x0), fabsf(x1)));
+                m = fmaxf(m, an[u] * fmaxf(col[u] < kk ? fabsf(x0) : 0.f, col[u] + 1 < kk ? fabsf(x1) : 0.f));
                 const unsigned e = c0 + u * 256 + threadIdx.x;
                 if (phi32 && e < nvec) reinterpret_cast<float2*>(phi32 + (long long)b * N * ld)[e] = float2{x0, x1};
             }
         }
     } else {
         for (unsigned e = blockIdx.x * 256 + threadIdx.x; e < total; e += n_part * 256) {
-            m = fmaxf(m, fabsf((float)a[e / (unsigned)ld]) * fabsf((float)P[e]));
+            const unsigned row = e / (unsigned)ld;
+            if (e - row * (unsigned)ld < kk) m = fmaxf(m, fabsf((float)a[row]) * fabsf((float)P[e]));
             if (sizeof(TR) == 8 && phi32) phi32[(long long)b * N * ld + e] = (float)P[e];
         }
     }
@@ -604,8 +616,10 @@ int dm_project_f16split_launch(dm_ctx* ctx, int B, int N, int D, int k, const TR
     if (!p.partial || !amax_part) return dm_fail(ctx, DM_ENOMEM, "dm_project: workspace not reserved");
     p.amax_part = amax_part; p.n_part = n_part;
     const size_t lds = (size_t)2 * PSTAGE * sizeof(_Float16);
-    // (its buffer loads take 32-bit byte offsets into a pair's arrays and dword-aligned descriptor rows)
-    const bool onepass_ok = (long long)N * ld * (long long)sizeof(TR) < (1ll << 31) - 4096 && (long long)N * D * 2 < (1ll << 31) && (D & 1) == 0;
+    // (its buffer loads take 32-bit byte offsets into a pair's arrays and dword-aligned descriptor rows: D even AND the
+    //  descriptors themselves on a dword boundary -- an fp16 view may start at any even address)
+    const bool onepass_ok = (long long)N * ld * (long long)sizeof(TR) < (1ll << 31) - 4096 && (long long)N * D * 2 < (1ll << 31) && (D & 1) == 0 &&
+                            (((uintptr_t)F) & 3) == 0;
     if (ctx->opt_proj_onepass && onepass_ok) {
         // one pass over the basis as it is (running scale per workgroup): no maxima pass, no fp32 copy
         proj2_params<TR> q;
@@ -627,7 +641,7 @@ int dm_project_f16split_launch(dm_ctx* ctx, int B, int N, int D, int k, const TR
         float* phi32 = (float*)dm_ws_take(ctx, (size_t)B * N * ld * 4);
         float* mass32 = (float*)dm_ws_take(ctx, (size_t)B * N * 4);
         if (!phi32 || !mass32) return dm_fail(ctx, DM_ENOMEM, "dm_project: workspace not reserved");
-        DM_LAUNCH(ctx, "project_absmax", proj_absmax_kernel<TR>, dim3(n_part + (cz ? 1 : 0), B), dim3(256), 0, Phi, mass, N, ld, amax_part, phi32,
+        DM_LAUNCH(ctx, "project_absmax", proj_absmax_kernel<TR>, dim3(n_part + (cz ? 1 : 0), B), dim3(256), 0, Phi, mass, N, ld, k, amax_part, phi32,
                   mass32, n_part, cz ? *cz : dm_c00_args<TR>{});
         proj_params<float> pf;
         pf.Phi = phi32; pf.mass = mass32; pf.F = p.F; pf.amax_part = p.amax_part; pf.n_part = p.n_part; pf.partial = p.partial;
@@ -636,7 +650,7 @@ int dm_project_f16split_launch(dm_ctx* ctx, int B, int N, int D, int k, const TR
         if (rc) return rc;
         DM_LAUNCH(ctx, "project_f16split_mfma", proj_f16split_kernel<float>, dim3(p.tiles_m * p.tiles_d * nsplit * B), dim3(256), lds, pf);
     } else {
-        DM_LAUNCH(ctx, "project_absmax", proj_absmax_kernel<TR>, dim3(n_part + (cz ? 1 : 0), B), dim3(256), 0, Phi, mass, N, ld, amax_part,
+        DM_LAUNCH(ctx, "project_absmax", proj_absmax_kernel<TR>, dim3(n_part + (cz ? 1 : 0), B), dim3(256), 0, Phi, mass, N, ld, k, amax_part,
                   (float*)nullptr, (float*)nullptr, n_part, cz ? *cz : dm_c00_args<TR>{});
         rc = dm_grant_lds(ctx, (const void*)proj_f16split_kernel<TR>, lds);
         if (rc) return rc;

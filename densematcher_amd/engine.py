@@ -223,7 +223,9 @@ class MatchEngine:
 
     def project(self, Phi, mass, F, k=None, out=None, exact=False):
         """Phi[:, :k]^T (mass * F)  ->  (B,k,D) f32.  fp16 descriptors use the fp16 matrix cores (split basis,
-        relative error ~1e-6); exact=True or fp32 descriptors use the float64 matrix cores."""
+        relative error ~1e-6); exact=True or fp32 descriptors use the float64 matrix cores.
+        The one-pass kernel ("proj_onepass" = 1) reads descriptor rows in dwords: fp16 descriptors that start at an odd element (a view
+        cut at an odd offset) take the two-launch kernels instead -- the same result to 2e-6 of sum |mass Phi| |F|, not the same bits."""
         sfx, Phi, mass = self._reals(Phi, mass)
         if not isinstance(F, torch.Tensor):
             F = torch.as_tensor(F)
@@ -251,7 +253,8 @@ class MatchEngine:
 
     def fmap_fit(self, Phi1, Phi2, a1, a2, F1, F2, lam1, lam2, w_descr, w_lap, k1=None, k2=None, check=True):
         """project(mesh 1) + project(mesh 2) + c00 + fmap_solve in one library call (dm_fmap_fit): the same C bit for bit; the
-        projected descriptors are not returned.  fp16 descriptors."""
+        projected descriptors are not returned.  fp16 descriptors (on a dword boundary for the one-pass projection, see project: a view that
+        starts at an odd element takes the two-launch kernels, C within 1e-6, not the same bits)."""
         sfx, Phi1, Phi2, a1, a2 = self._reals(Phi1, Phi2, a1, a2)
         F1 = self._dev(F1, torch.float16, "F1")
         F2 = self._dev(F2, torch.float16, "F2")
