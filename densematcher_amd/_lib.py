@@ -83,6 +83,8 @@ SIGNATURES = {
     "dm_fmn_quad_form": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dm_fmn_cclb": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "dm_spectral_signatures": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
+    "dm_shape_diff_f64": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p]),
+    "dm_pullback_forms_f64": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

@@ -722,6 +722,30 @@ class MatchEngine:
                   (8, "a face index or a column of W lies outside the mesh's vertices"),
                   (16, "a vertex that no face references"))
 
+    def _stiffness_rows(self, W, n, who, b):
+        """the stiffness matrix of mesh b (n vertices) as ELL rows (cols (n, nnz) int32, w (n, nnz) float64) on the device: a SciPy
+        sparse matrix is converted row by row in CSR order and padded with col = -1, val = 0; (cols, w) device rows (those of
+        laplacian_ell) pass through"""
+        import numpy as np
+        import scipy.sparse as sp
+        if sp.issparse(W):
+            Wc = sp.csr_matrix(W)
+            if Wc.shape != (n, n):
+                raise ValueError(f"{who}: mesh {b}: W is {Wc.shape}, expected {(n, n)}")
+            rl = np.diff(Wc.indptr)
+            w = max(1, int(rl.max()))
+            cols_h = np.full((n, w), -1, np.int32)
+            vals_h = np.zeros((n, w), np.float64)
+            pos = np.arange(Wc.nnz) - np.repeat(Wc.indptr[:-1], rl)
+            r = np.repeat(np.arange(n), rl)
+            cols_h[r, pos] = Wc.indices
+            vals_h[r, pos] = Wc.data
+            return torch.as_tensor(cols_h).to(self.device), torch.as_tensor(vals_h).to(self.device)
+        cols_d, w_d = W
+        if cols_d.shape[0] != n or w_d.shape != cols_d.shape:
+            raise ValueError(f"{who}: mesh {b}: device rows of shape {tuple(cols_d.shape)} for {n} vertices")
+        return cols_d, w_d
+
     def heat_geodesic_factor(self, meshes, t):
         """Factor the two systems of the heat method (pyFM geometry.heat_geodmat: A + tW and W, geometry.py:716-718) for a batch
         of meshes, on the device (dm_heat_geodesic_factor: dense float64 Cholesky, W grounded at vertex 0).
@@ -730,7 +754,6 @@ class MatchEngine:
         on a mesh of more than one connected component (vertices that no face references included), masses that are not one
         third of the adjacent face areas (heat_geodesic_check), a face of zero area or a system that is not positive definite.  Returns the factors (a dict holding the device buffer) for heat_geodesic."""
         import numpy as np
-        import scipy.sparse as sp
         Bn = len(meshes)
         if Bn == 0:
             raise ValueError("heat_geodesic_factor: no meshes")
@@ -739,24 +762,7 @@ class MatchEngine:
         for b, (V, F, W, mass) in enumerate(meshes):
             heat_geodesic_check(V, F, mass, b)
             n = len(V)
-            if sp.issparse(W):
-                Wc = sp.csr_matrix(W)
-                if Wc.shape != (n, n):
-                    raise ValueError(f"heat_geodesic_factor: mesh {b}: W is {Wc.shape}, expected {(n, n)}")
-                rl = np.diff(Wc.indptr)
-                w = max(1, int(rl.max()))
-                cols_h = np.full((n, w), -1, np.int32)
-                vals_h = np.zeros((n, w), np.float64)
-                pos = np.arange(Wc.nnz) - np.repeat(Wc.indptr[:-1], rl)
-                r = np.repeat(np.arange(n), rl)
-                cols_h[r, pos] = Wc.indices
-                vals_h[r, pos] = Wc.data
-                rows.append((torch.as_tensor(cols_h).to(self.device), torch.as_tensor(vals_h).to(self.device)))
-            else:
-                cols_d, w_d = W
-                if cols_d.shape[0] != n or w_d.shape != cols_d.shape:
-                    raise ValueError(f"heat_geodesic_factor: mesh {b}: device rows of shape {tuple(cols_d.shape)} for {n} vertices")
-                rows.append((cols_d, w_d))
+            rows.append(self._stiffness_rows(W, n, "heat_geodesic_factor", b))
             n_verts.append(n)
         N = max(n_verts)
         nt = max(len(m[1]) for m in meshes)
@@ -1828,6 +1834,117 @@ class MatchEngine:
             self.ctx, B, N, ip(nv), K, _ptr(Phi), ld, {"HKS": 0, "WKS": 1}[kind], num, _ptr(t), _ptr(mu), _ptr(denom), ip(k0), P, ip(lm),
             plain, 1 if out_dtype == torch.float32 else 0, _ptr(out)))
         return out
+
+    # ------------------------------------------------------------- shape difference operators (dm_shape_diff_f64, dm_pullback_forms_f64)
+    SD_MAX_K1, SD_MAX_K2 = 256, 768
+
+    def shape_difference(self, FM, lam1=None, lam2=None, k1=None):
+        """Area and conformal shape difference operators of B functional maps (pyFM shape_difference.py:20, :44), one call:
+        SD_a = FM^T FM and SD_c = pinv(diag(lam1[:k1])) FM^T (lam2[:k2, None] * FM), both (B, k1, k1) float64 on the device
+        (SD_c is None when the eigenvalues are not given).
+        FM (B, k2, ldf) with k1 <= ldf columns in use (k1: default all), lam1 (B, >= k1), lam2 (B, >= k2); NumPy arrays or GPU
+        tensors.  k1 <= 256, k2 <= 768 (ValueError otherwise).  No host synchronisation."""
+        FM = self._dev(FM, torch.float64, "FM")
+        if FM.dim() != 3:
+            raise ValueError("shape_difference: FM must be (B,k2,k1)")
+        B, k2, ldf = FM.shape
+        k1 = ldf if k1 is None else int(k1)
+        if not 0 < k1 <= ldf:
+            raise ValueError(f"shape_difference: k1 = {k1} with {ldf} columns")
+        if (lam1 is None) != (lam2 is None):
+            raise ValueError("shape_difference: the conformal operator needs the eigenvalues of both meshes")
+        SDa = torch.empty((B, k1, k1), dtype=torch.float64, device=self.device)
+        SDc, l1, l2 = None, 0, 0
+        if lam1 is not None:
+            lam1, lam2 = self._dev(lam1, torch.float64, "lam1"), self._dev(lam2, torch.float64, "lam2")
+            if lam1.dim() != 2 or lam2.dim() != 2 or lam1.shape[0] != B or lam2.shape[0] != B or lam1.shape[1] < k1 or lam2.shape[1] < k2:
+                raise ValueError(f"shape_difference: a ({k2},{k1}) map needs lam1 (B,>={k1}) and lam2 (B,>={k2})")
+            SDc, l1, l2 = torch.empty((B, k1, k1), dtype=torch.float64, device=self.device), lam1.shape[1], lam2.shape[1]
+        self._chk(self.lib.dm_shape_diff_f64(self.ctx, B, k1, k2, _ptr(FM), ldf, _ptr(lam1), l1, _ptr(lam2), l2, _ptr(SDa), _ptr(SDc)))
+        return SDa, SDc
+
+    def _vertex_maps(self, p21, B, N2, N1, nv1, nv2, who):
+        """B vertex maps (B, N2) into meshes of N1 (nv1[b]) vertices as a non-negative int32 device tensor, with NumPy's index rules
+        -- integers in [-n1, n1), negatives counted from the end, IndexError otherwise -- checked on the device (one synchronisation);
+        entries past nv2[b] are not looked at and come out 0"""
+        import numpy as np
+        p = p21 if isinstance(p21, torch.Tensor) else torch.as_tensor(np.asarray(p21))
+        if p.dtype.is_floating_point or p.dtype == torch.bool:
+            raise IndexError(f"{who}: arrays used as indices must be of integer type")
+        if tuple(p.shape) != (B, N2):
+            raise ValueError(f"{who}: p21 must be (B,N2)")
+        p = p.to(self.device)
+        n1 = torch.full((B, 1), N1, dtype=torch.int64, device=self.device) if nv1 is None else torch.as_tensor(nv1.astype(np.int64)).to(self.device)[:, None]
+        live = None if nv2 is None else (torch.arange(N2, device=self.device)[None, :] < torch.as_tensor(nv2.astype(np.int64)).to(self.device)[:, None])
+        bad = (p < -n1) | (p >= n1)
+        if live is not None:
+            bad &= live
+        if bool(bad.any()):
+            b, i = (int(x) for x in bad.nonzero()[0])
+            raise IndexError(f"{who}: pair {b}: index {int(p[b, i])} is out of bounds for axis 0 with size {int(n1[b, 0])}")
+        p = torch.where(p < 0, p + n1, p)
+        if live is not None:
+            p = torch.where(live, p, torch.zeros_like(p))
+        return p.to(torch.int32).contiguous()
+
+    def pullback_forms(self, p21, Phi1, W, mass2, k1, lam1=None, n_verts1=None, n_verts2=None):
+        """The quadratic forms of the target mesh pulled back through vertex maps (pyFM shape_difference.py:94-96, the 'semican'
+        operators), B pairs in one launch: with X = Phi1[p21, :k1]
+            Ga = X^T diag(mass2) X,    Gw = X^T (W X)   -- or pinv(diag(lam1[:k1])) X^T (W X), the conformal operator, when lam1 is given.
+        p21 (B, N2) integers with NumPy's index rules (IndexError for an entry outside [-n1, n1)), Phi1 (B, N1, ld1 >= k1) float64,
+        mass2 (B, N2), lam1 (B, >= k1); NumPy arrays or GPU tensors.  W: per pair a SciPy sparse matrix or the (cols, w) device rows
+        (n, nnz) of laplacian_ell, as heat_geodesic_factor takes them -- or one (cols (B, N2, nnz), w (B, N2, nnz)) pair of tensors for
+        the whole batch.  n_verts1 / n_verts2 (B,): the vertex counts of padded batches.  Returns (Ga, Gw), (B, k1, k1) float64 on the
+        device.  A pair's bits do not depend on the other pairs or on the padding.  One host synchronisation: the check of p21."""
+        import numpy as np
+        Phi1 = self._dev(Phi1, torch.float64, "Phi1")
+        mass2 = self._dev(mass2, torch.float64, "mass2")
+        if Phi1.dim() != 3 or mass2.dim() != 2 or mass2.shape[0] != Phi1.shape[0]:
+            raise ValueError("pullback_forms: Phi1 must be (B,N1,ld1), mass2 (B,N2)")
+        B, N1, ld1 = Phi1.shape
+        N2 = mass2.shape[1]
+        k1 = int(k1)
+        if not 0 < k1 <= ld1:
+            raise ValueError(f"pullback_forms: k1 = {k1} with {ld1} eigenvector columns")
+        nv = []
+        for name, n_verts, N in (("n_verts1", n_verts1, N1), ("n_verts2", n_verts2, N2)):
+            a = None if n_verts is None else np.ascontiguousarray(np.broadcast_to(np.asarray(n_verts, np.int64), (B,)), dtype=np.int32)
+            if a is not None and (a.min() < 1 or a.max() > N):
+                raise ValueError(f"pullback_forms: {name} must lie in [1, {N}]")
+            nv.append(a)
+        nv1, nv2 = nv
+        # the vertex maps: NumPy's rules against each pair's own source mesh, checked before anything is launched
+        p = self._vertex_maps(p21, B, N2, N1, nv1, nv2, "pullback_forms")
+        # ---- the stiffness rows
+        if isinstance(W, tuple) and len(W) == 2 and isinstance(W[0], torch.Tensor) and W[0].dim() == 3:
+            cols, wv = self._dev(W[0], torch.int32, "cols"), self._dev(W[1], torch.float64, "w")
+            if cols.shape[:2] != (B, N2) or wv.shape != cols.shape:
+                raise ValueError(f"pullback_forms: batched device rows must be (B,N2,nnz), got {tuple(cols.shape)}")
+            nnz = int(cols.shape[2])
+        else:
+            if len(W) != B:
+                raise ValueError(f"pullback_forms: {len(W)} stiffness matrices for {B} pairs")
+            rows = [self._stiffness_rows(Wb, N2 if nv2 is None else int(nv2[b]), "pullback_forms", b) for b, Wb in enumerate(W)]
+            nnz = max(int(c.shape[1]) for c, _ in rows)
+            cols = torch.full((B, N2, nnz), -1, dtype=torch.int32, device=self.device)
+            wv = torch.zeros((B, N2, nnz), dtype=torch.float64, device=self.device)
+            for b, (c, w) in enumerate(rows):
+                cols[b, :c.shape[0], :c.shape[1]] = c.to(self.device, torch.int32)
+                wv[b, :w.shape[0], :w.shape[1]] = w.to(self.device, torch.float64)
+        if nnz < 1:
+            raise ValueError("pullback_forms: empty stiffness rows")
+        ld_l1 = 0
+        if lam1 is not None:
+            lam1 = self._dev(lam1, torch.float64, "lam1")
+            if lam1.dim() != 2 or lam1.shape[0] != B or lam1.shape[1] < k1:
+                raise ValueError(f"pullback_forms: lam1 must be (B,>={k1})")
+            ld_l1 = lam1.shape[1]
+        Ga = torch.empty((B, k1, k1), dtype=torch.float64, device=self.device)
+        Gw = torch.empty((B, k1, k1), dtype=torch.float64, device=self.device)
+        ip = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        self._chk(self.lib.dm_pullback_forms_f64(self.ctx, B, N1, N2, k1, _ptr(p), _ptr(Phi1), ld1, _ptr(cols), _ptr(wv), nnz, _ptr(mass2),
+                                                 ip(nv1), ip(nv2), _ptr(lam1), ld_l1, _ptr(Ga), _ptr(Gw)))
+        return Ga, Gw
 
     # ------------------------------------------------------------------ the hot path, one batch
     def match(self, batch, k=None, w_descr=1e4, w_lap=1e3, knn=True, ind=True, check=False):

@@ -178,6 +178,8 @@ class FunctionalMapping:
         self._FM_base = None
         self._FM_icp = None
         self._FM_zo = None
+        self.SD_a = None                           # functional.py:72-73 (compute_SD itself sets D_a / D_c: the reference's names, both kept)
+        self.SD_c = None
         self._k1, self._k2 = None, None
         self.optimizer = optimizer
         self.partial = partial
@@ -478,6 +480,14 @@ class FunctionalMapping:
         self._FM_zo = refine.mesh_zoomout_refine(self.FM, self.mesh1, self.mesh2, nit, step=step, subsample=sub, verbose=verbose)
         if overwrite:
             self.FM_type = 'zoomout'
+
+    def compute_SD(self):
+        """functional.py:619-627: the area and conformal shape difference operators of the fitted map, as D_a / D_c.  A NumPy map
+        takes the host products (the reference's bits), a map held as a GPU tensor dm_shape_diff_f64."""
+        if not self.fitted:
+            raise ValueError("The Functional map must be fit before computing the shape difference")
+        self.D_a = spectral.area_SD(self.FM)
+        self.D_c = spectral.conformal_SD(self.FM, self.mesh1.eigenvalues, self.mesh2.eigenvalues)
 
     # ---------------------------------------------------------------- small helpers (functional.py:730-831)
     def project(self, func, k=None, mesh_ind=1):

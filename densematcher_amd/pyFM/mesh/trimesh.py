@@ -622,6 +622,17 @@ class TriMesh:
     def l2_inner(self, func1, func2):
         return np.einsum('np,np->p', func1, self.A @ func2) if func1.ndim > 1 else func1 @ (self.A @ func2)
 
+    def h1_sqnorm(self, func):
+        """squared H^1_0 norm f^T W f of one (n,) or several (n, p) functions (trimesh.py:784-800)"""
+        return self.h1_inner(func, func)
+
+    def h1_inner(self, func1, func2):
+        """f1^T W f2 with the stiffness matrix W, per column for (n, p) functions (trimesh.py:802-827); host products"""
+        assert func1.shape == func2.shape, "Shapes must be equal"
+        if func1.ndim == 1:
+            return func1 @ self.W @ func2
+        return np.einsum('np,np->p', func1, self.W @ func2)
+
     def integrate(self, func):
         return func.T @ self.A.diagonal()
 

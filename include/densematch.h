@@ -692,6 +692,39 @@ int dm_icp_f64(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
                const double* Phi1, int ld1, const double* Phi2, int ld2,
                const double* C0, int nit, double* Cout, double* resid /*nullable*/, int32_t* info);
 
+/* ---- shape difference operators ---------------------------------------------------
+ * Replaces pyFM/spectral/shape_difference.py:6-98 (area_SD, conformal_SD, compute_SD), batched: B pairs (or B candidate maps) per call.
+ * In both entry points inv1 stands for np.linalg.pinv(np.diag(lam1[:k1])) (shape_difference.py:44, :96), which is diagonal:
+ *   inv1[i] = 1 / lam1[i]  if |lam1[i]| > 1e-15 max_j<k1 |lam1[j]|,  else exactly 0      (pinv's cut-off at its default rcond)
+ * and a cut row leaves as exact +0.
+ *   dm_shape_diff_f64      from a functional map FM (B,k2,ldf) fp64, ldf >= k1 (the 'spectral' form):
+ *                            SDa = FM^T FM                                              (B,k1,k1)   shape_difference.py:20
+ *                            SDc[i][j] = inv1[i] sum_l FM[l][i] (lam2[l] FM[l][j])      (B,k1,k1)   shape_difference.py:44
+ *                          lam1 (B,ld_l1), lam2 (B,ld_l2) fp64 device, ld_l1 >= k1, ld_l2 >= k2 (read only for SDc).  Either output may
+ *                          be null.  One workgroup per pair and 64 x 64 tile on the f64 matrix cores, l = 0 .. k2 - 1 in order.
+ *                          Limits: k1 <= 256, k2 <= 768 (3 k1 at k1 = 256), else DM_EINVAL.
+ *   dm_pullback_forms_f64  from a vertex map p21 (B,N2) int32 (the 'semican' form, shape_difference.py:94-96), X = Phi1[p21, :k1]:
+ *                            Ga = X^T diag(mass2) X                                     (B,k1,k1)
+ *                            Gw = X^T (W2 X),  or diag(inv1) X^T (W2 X) when lam1 is given (the conformal operator itself)
+ *                          Phi1 (B,N1,ld1) fp64; W2 as stiffness rows in ELL: ell_cols (B,N2,nnz) int32, w_vals (B,N2,nnz) fp64, the
+ *                          layout dm_laplacian_ell writes (`w`, padded with col = row, val = 0) or a host CSR padded with col = -1: a
+ *                          column outside [0, n_verts2[b]) contributes nothing.  mass2 (B,N2) fp64.  n_verts1 / n_verts2 (B) HOST,
+ *                          nullable = N1 / N2: the vertex counts of a padded batch; rows of p21, mass2 and W2 past n_verts2[b] and
+ *                          rows of Phi1 past n_verts1[b] are never read.  lam1 (B,ld_l1) fp64 device, nullable.  Either output may be
+ *                          null.  A p21 entry outside [0, n_verts1[b]) is clamped -- nothing is read outside Phi1; callers check
+ *                          their maps.  A row of W2 X is formed in registers inside the contraction kernel (nnz gathered rows in
+ *                          ELL order), not written to memory.  Limit: k1 <= 256, else DM_EINVAL.  With n_verts1 / n_verts2 the call
+ *                          synchronises the stream once (their upload).
+ * Every sum runs in a fixed order that depends on the pair alone (vertices in index order inside 512-vertex partials, the partials in
+ * order): a pair's bits do not depend on B, on what shares the call, on the padding or on the row strides.  No floating-point
+ * atomics. */
+int dm_shape_diff_f64(dm_ctx* ctx, int B, int k1, int k2, const double* FM, int ldf, const double* lam1 /*nullable*/, int ld_l1,
+                      const double* lam2 /*nullable*/, int ld_l2, double* SDa /*nullable*/, double* SDc /*nullable*/);
+int dm_pullback_forms_f64(dm_ctx* ctx, int B, int N1, int N2, int k1, const int32_t* p21, const double* Phi1, int ld1,
+                          const int32_t* ell_cols, const double* w_vals, int nnz, const double* mass2,
+                          const int32_t* n_verts1 /*host, nullable*/, const int32_t* n_verts2 /*host, nullable*/,
+                          const double* lam1 /*nullable*/, int ld_l1, double* Ga /*nullable*/, double* Gw /*nullable*/);
+
 #ifdef __cplusplus
 }
 #endif
