@@ -715,6 +715,132 @@ class MatchEngine:
         self._chk(self.lib.dm_laplacian_ell(self.ctx, Bn, N, nt, _ptr(rows), nnz, _ptr(nv_d), _ptr(cols), _ptr(vals), _ptr(mass32), _ptr(w), _ptr(mass64)))
         return {"cols": cols, "vals": vals, "mass32": mass32, "w": w, "mass64": mass64, "nnz": nnz, "n_verts": n_verts}
 
+    # ------------------------------------------------------------- DiffusionNet operators (dm_dnet_*)
+    def _dnet_assemble(self, V, F, normals):
+        """dm_dnet_rows + dm_dnet_ell of the meshes (V[b] (n_b, 3) float64, F[b] (m_b, 3) int32 NumPy arrays; normals: a list of
+        (n_b, 3) arrays or None), padded as laplacian_ell pads.  Returns the dict of device tensors."""
+        import numpy as np
+        from .diffusion_net import _host
+        Bn = len(V)
+        n_verts = [int(v.shape[0]) for v in V]
+        N, nt = max(n_verts), max(int(f.shape[0]) for f in F)
+        tri_h = np.full((Bn, nt, 3), -1, np.int32)
+        vert_h = np.zeros((Bn, N, 3), np.float64)
+        nrm_h = np.zeros((Bn, N, 3), np.float64) if normals is not None else None
+        for b in range(Bn):
+            tri_h[b, :len(F[b])] = F[b]
+            vert_h[b, :n_verts[b]] = V[b]
+            if nrm_h is not None:
+                nrm_h[b, :n_verts[b]] = normals[b]
+        # (through _dev: it refuses a call under another stream than the engine's, where the allocator could recycle the scratch below
+        #  while the context's stream still uses it)
+        tri_d = self._dev(tri_h, torch.int32, "tri")
+        vert_d = self._dev(vert_h, torch.float64, "verts")
+        nrm_d = self._dev(nrm_h, torch.float64, "normals") if nrm_h is not None else None
+        nv_d = self._dev(np.asarray(n_verts, np.int32), torch.int32, "n_verts") if min(n_verts) < N else None
+        rows = torch.empty(int(self.lib.dm_dnet_rows_bytes(Bn, N, nt)), dtype=torch.uint8, device=self.device)
+        frames = torch.empty((Bn, N, 3, 3), dtype=torch.float64, device=self.device)
+        info = torch.empty((Bn,), dtype=torch.int32, device=self.device)
+        mx = C.c_int(0)
+        self._chk(self.lib.dm_dnet_rows(self.ctx, Bn, N, nt, _ptr(tri_d), _ptr(vert_d), _ptr(nrm_d), _ptr(nv_d), _host.DENOM_EPS, _host.GRAD_EPS,
+                                        _ptr(rows), _ptr(frames), _ptr(info), C.byref(mx)))
+        nnz = int(mx.value)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+        out = {"frames": frames, "info": info, "nnz": nnz, "n_verts": n_verts,
+               "row_len": torch.empty((Bn, N), dtype=torch.int32, device=self.device),
+               "cols": torch.empty((Bn, N, nnz), dtype=torch.int32, device=self.device),
+               "l": f64(Bn, N, nnz), "vals": f64(Bn, N, nnz), "gx": f64(Bn, N, nnz), "gy": f64(Bn, N, nnz), "mass64": f64(Bn, N),
+               "mass32": torch.empty((Bn, N), dtype=torch.float32, device=self.device)}
+        self._chk(self.lib.dm_dnet_ell(self.ctx, Bn, N, nt, _ptr(rows), nnz, _ptr(nv_d), _host.MASS_EPS, _host.MASS_EPS, _ptr(out["row_len"]),
+                                       _ptr(out["cols"]), _ptr(out["l"]), _ptr(out["vals"]), _ptr(out["gx"]), _ptr(out["gy"]), _ptr(out["mass64"]),
+                                       _ptr(out["mass32"])))
+        return out
+
+    def diffusion_operators(self, verts_list, faces_list, k_eig, normals=None):
+        """What diffusion_net.geometry.compute_operators precomputes (reference diffusion_net/geometry.py:275-391), for a batch of
+        meshes in one device call: dm_dnet_rows / dm_dnet_ell, then eigenbasis(ell=...) on M'^-1/2 (L + 1e-8 I) M'^-1/2.
+        verts_list / faces_list: (n_b, 3) / (m_b, 3) arrays; normals: None or a list with an (n_b, 3) array or None per mesh.
+        A mesh for which the device reports an undefined normal (bit 1 of info) gets its normals from the host -- the reference's
+        repair sequence, literally -- and runs again with them.
+        Returns a list with, per mesh, the dict frames (n,3,3), mass (n), row_len (n) int32, cols (n,nnz) int32, l / gx / gy (n,nnz),
+        evals (k), evecs (n,k): float64 tensors on the device, padding rows cut off, entries q < row_len[i] of row i real; and
+        info: the first pass's info word of the mesh."""
+        import numpy as np
+        from .diffusion_net import _host
+        Bn = len(verts_list)
+        if Bn == 0:
+            return []
+        V = [np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64) for v in verts_list]
+        F = [np.ascontiguousarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f) for f in faces_list]
+        for b in range(Bn):
+            if V[b].ndim != 2 or V[b].shape[1] != 3 or V[b].shape[0] == 0:
+                raise ValueError(f"diffusion_operators: mesh {b}: vertices must be (n, 3)")
+            if F[b].size == 0:
+                raise NotImplementedError("diffusion_operators: point clouds (no faces) are not built")
+            if F[b].ndim != 2 or F[b].shape[1] != 3 or F[b].min() < 0 or F[b].max() >= V[b].shape[0]:
+                raise ValueError(f"diffusion_operators: mesh {b}: faces must be (m, 3) indices into the {V[b].shape[0]} vertices")
+            F[b] = F[b].astype(np.int32)
+        given = [None] * Bn if normals is None else [None if g is None else np.asarray(g.detach().cpu().numpy() if isinstance(g, torch.Tensor) else g, np.float64)
+                                                      for g in normals]
+        have, lack = [b for b in range(Bn) if given[b] is not None], [b for b in range(Bn) if given[b] is None]
+        parts, first_info = [None] * Bn, [0] * Bn
+
+        def run(idx, nrm):
+            out = self._dnet_assemble([V[b] for b in idx], [F[b] for b in idx], nrm)
+            info = out["info"].cpu().numpy()
+            for q, b in enumerate(idx):
+                parts[b] = (out, q)
+                if nrm is None:
+                    first_info[b] = int(info[q])
+            return info
+
+        if lack:
+            info = run(lack, None)
+            redo = [b for q, b in enumerate(lack) if info[q] & 1]
+            for b in redo:
+                given[b] = _host.vertex_normals(V[b], F[b].astype(np.int64))
+            have = sorted(have + redo)
+        if have:
+            run(have, [given[b] for b in have])
+        res = [None] * Bn
+        groups = {}
+        for b in range(Bn):
+            groups.setdefault(id(parts[b][0]), []).append(b)
+        # eigenbasis() chooses between the filtered iteration and the dense route from the SMALLEST mesh of its batch (and the dense
+        # route takes at most 2048 padded vertices): meshes are solved with the partners that take the same route as they would alone,
+        # each group cut to its own largest mesh, so a small mesh neither drags a large one to the dense route nor changes its own
+        guard = next((g for g in range(12, 33) if (int(k_eig) + g) % 32 == 0), 32)
+        by_route = {}
+        for key, idx in groups.items():
+            for b in idx:
+                by_route.setdefault((key, 2 * (int(k_eig) + guard) > V[b].shape[0]), []).append(b)
+        for idx in by_route.values() if k_eig > 0 else groups.values():
+            out = parts[idx[0]][0]
+            if k_eig > 0:
+                sel = torch.as_tensor([parts[b][1] for b in idx], device=self.device)
+                Ng = max(V[b].shape[0] for b in idx)
+                cut = lambda t: t[sel, :Ng].contiguous()
+                out = {key: cut(out[key]) for key in ("frames", "mass64", "row_len", "cols", "l", "gx", "gy", "vals", "mass32")}
+                out["nnz"], out["n_verts"] = parts[idx[0]][0]["nnz"], [V[b].shape[0] for b in idx]
+                for q, b in enumerate(idx):
+                    parts[b] = (out, q)
+                ell = {"cols": out["cols"], "vals": out["vals"], "mass32": out["mass32"], "nnz": out["nnz"], "n_verts": out["n_verts"]}
+                lam, Phi, _, _ = self.eigenbasis(None, None, int(k_eig), guard=guard, ell=ell)
+                # dm_eigenbasis solves the problem of the fp32-rounded masses M' (Phi^T M' Phi = I).  The operators carry the float64
+                # masses M: Phi <- Phi (Phi^T M Phi)^-1/2, the symmetric orthonormalisation, with G = I + E, |E| ~ 1e-8:
+                # G^-1/2 = I - E/2 + 3/8 E^2 to 1e-24.  The eigenvalues move by E's second order; they stay as returned.
+                G = torch.matmul(Phi.transpose(1, 2), out["mass64"].unsqueeze(-1) * Phi)
+                E = G - torch.eye(G.shape[-1], dtype=G.dtype, device=G.device)
+                Phi = Phi - torch.matmul(Phi, 0.5 * E - 0.375 * torch.matmul(E, E))
+                lam = torch.clamp(lam, min=0.0)
+            for b in idx:
+                q, n = parts[b][1], V[b].shape[0]
+                res[b] = {"frames": out["frames"][q, :n], "mass": out["mass64"][q, :n], "row_len": out["row_len"][q, :n], "cols": out["cols"][q, :n],
+                          "l": out["l"][q, :n], "gx": out["gx"][q, :n], "gy": out["gy"][q, :n], "info": first_info[b],
+                          "evals": lam[q] if k_eig > 0 else torch.zeros((0,), dtype=torch.float64, device=self.device),
+                          "evecs": Phi[q, :n] if k_eig > 0 else torch.zeros((n, 0), dtype=torch.float64, device=self.device)}
+        return res
+
     # ------------------------------------------------------------- heat-method geodesics (dm_heat_geodesic_*)
     _GEOD_INFO = ((1, "A + tW is not positive definite"),
                   (2, "the grounded stiffness matrix W is not positive definite (more than one connected component?)"),

@@ -464,6 +464,37 @@ int dm_laplacian_rows(dm_ctx* ctx, int B, int N, int nt, const int32_t* tri, con
 int dm_laplacian_ell(dm_ctx* ctx, int B, int N, int nt, const void* rows, int nnz, const int32_t* n_verts /*nullable*/,
                      int32_t* ell_cols, double* ell_vals, float* mass32, double* w_vals /*nullable*/, double* mass64 /*nullable*/);
 
+/* ---- DiffusionNet operators ----------------------------------------------------------------------------------------------
+ * What diffusion_net.geometry.compute_operators builds besides its eigensolve (diffusion_net/geometry.py:151-391), for B meshes padded
+ * to N vertices and nt triangles (triangles (-1,-1,-1) pad tri; n_verts (B, nullable): the real vertex count of each), float64:
+ *   frames (B,N,3,3)  rows bx, by, n.  n = the normalised sum over the incident corners of the unit face normals raw / (|raw| + 1e-6),
+ *                     or normals (B,N,3) when given; bx = c - (c.n) n over (norm + 1e-6) with c = e_x where |n.e_x| < 0.9, else e_y;
+ *                     by = n x bx.  A vertex whose sum has no direction (unreferenced, exactly cancelling faces) gets a zero frame and
+ *                     sets bit 1 of info[b] (device, (B)): the caller repairs the normals and calls again with them.
+ *   L                 the weak cotangent Laplacian: for each corner k opposite the edge (i, j), cot = (v_i - v_k).(v_j - v_k) /
+ *                     (|(v_i - v_k) x (v_j - v_k)| + denom_eps); L_ii, L_jj += cot / 2, L_ij, L_ji -= cot / 2.  An entry exists for every
+ *                     pair of vertices that share a face, whatever its value.
+ *   mass              a third of the incident areas + mass_eps * mean over the mesh.
+ *   gradX, gradY      per vertex i over the off-diagonal columns j of its row of L: t_j = ((v_j - v_i).bx_i, (v_j - v_i).by_i),
+ *                     M = sum_j t_j t_j^T + grad_eps I, g_j = M^-1 t_j (first / second component), g_self = -sum_j g_j in the
+ *                     diagonal slot; a vertex without neighbours keeps the single entry g_self = 0.
+ * A vertex's contributions are summed in a fixed order: a mesh gives the same bits whatever else shares the call.
+ *   dm_dnet_rows  assembly into rows (dm_dnet_rows_bytes of device memory); writes frames and info, reports max_row (host): the longest
+ *                 row (<= 64 entries: a vertex of more than 63 neighbours is DM_EINVAL, as in dm_laplacian_rows).
+ *   dm_dnet_ell   the rows at the ELL width nnz >= max_row: row_len (B,N); ell_cols (B,N,nnz) sorted by column and padded with (col = row,
+ *                 val = 0), the layout dm_laplacian_ell writes; l_vals, gx_vals, gy_vals on those columns; ell_vals = M'^-1/2 (L + shift I)
+ *                 M'^-1/2 with M' = the masses rounded to fp32 (mass32), the operand of dm_eigenbasis; mass64.  Padding vertices: zero
+ *                 frames and gradient rows, unit mass, a decoupled row at the Gershgorin bound of their mesh's operand.
+ * Both calls refuse (DM_EINVAL) an n_verts[b] outside [1, N]; dm_dnet_ell also an nnz below the longest row that dm_dnet_rows left in
+ * `rows`.  The checks read a few words back from the device: dm_dnet_rows synchronises the stream twice, dm_dnet_ell once (twice with
+ * n_verts). */
+size_t dm_dnet_rows_bytes(int B, int N, int nt);
+int dm_dnet_rows(dm_ctx* ctx, int B, int N, int nt, const int32_t* tri, const double* verts, const double* normals /*nullable*/,
+                 const int32_t* n_verts /*nullable*/, double denom_eps, double grad_eps, void* rows, double* frames, int32_t* info /*device*/,
+                 int* max_row /*host*/);
+int dm_dnet_ell(dm_ctx* ctx, int B, int N, int nt, const void* rows, int nnz, const int32_t* n_verts /*nullable*/, double mass_eps, double shift,
+                int32_t* row_len, int32_t* ell_cols, double* l_vals, double* ell_vals, double* gx_vals, double* gy_vals, double* mass64, float* mass32);
+
 /* ---- heat-method geodesic distances ------------------------------------------------
  * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
  * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors
