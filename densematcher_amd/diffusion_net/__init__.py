@@ -1,3 +1,3 @@
-"""DiffusionNet's operator precomputation (diffusion_net.geometry of the reference) with the reference's names; the network itself
-(layers, weights, forward pass) stays with PyTorch and is not part of this package."""
-from . import geometry, utils  # noqa: F401
+"""DiffusionNet with the reference's names: the operator precomputation (diffusion_net.geometry) and the network (diffusion_net.layers:
+the reference's modules and state_dict keys, with an inference route through fp32 HIP kernels next to the PyTorch expressions)."""
+from . import geometry, layers, utils  # noqa: F401

@@ -841,6 +841,158 @@ class MatchEngine:
                           "evecs": Phi[q, :n] if k_eig > 0 else torch.zeros((n, 0), dtype=torch.float64, device=self.device)}
         return res
 
+    # ------------------------------------------------------------- DiffusionNet forward (dm_dnet_*_f32)
+    def _dnet_mat(self, t, name):
+        """(tensor, ld) of an fp32 matrix operand, (B, N, W) or (R, W).  It is passed as it lies in memory when its elements of a row are
+        adjacent and its rows evenly spaced (row stride ld >= W, batch stride N ld) -- a parameter, a column slice of a wider buffer,
+        a padded view --, and copied otherwise."""
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.dtype != torch.float32:
+            t = self._dev(t, torch.float32, name)
+        elif torch.cuda.current_stream(self.device).cuda_stream != self.stream.cuda_stream:
+            raise RuntimeError("MatchEngine is bound to the stream it was created on; create one engine per stream")
+        if t.dim() == 2:
+            R, W = t.shape
+            ld = t.stride(0) if R > 1 else max(W, 1)
+            if (W == 1 or t.stride(1) == 1) and ld >= W:
+                return t, int(ld)
+            return t.contiguous(), int(W)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected a (B, N, W) or (N, W) tensor, got {tuple(t.shape)}")
+        Bn, N, W = t.shape
+        ld = t.stride(1) if N > 1 else (t.stride(0) if Bn > 1 else W)
+        if (W == 1 or t.stride(2) == 1) and ld >= W and (Bn == 1 or t.stride(0) == N * ld):
+            return t, int(ld)
+        return t.contiguous(), int(W)
+
+    def _dnet_counts(self, n_verts, Bn):
+        if n_verts is None:
+            return None
+        nv = self._dev(n_verts, torch.int32, "n_verts")
+        if nv.shape != (Bn,):
+            raise ValueError(f"n_verts: expected {Bn} counts, got {tuple(nv.shape)}")
+        return nv
+
+    def _dnet_out(self, out, Bn, N, C, name):
+        if out is None:
+            return torch.empty((Bn, N, C), dtype=torch.float32, device=self.device), C
+        if out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != (Bn, N, C):
+            raise ValueError(f"{name}: out must be a float32 ({Bn}, {N}, {C}) tensor on {self.device}")
+        o, ld = self._dnet_mat(out, name)
+        if o is not out:
+            raise ValueError(f"{name}: out must have adjacent elements in a row and evenly spaced rows")
+        return out, ld
+
+    def dnet_linear(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None):
+        """out[b,i,:] = act(concat(srcs)[b,i,:] weight^T + bias) + resid[b,i,:] (dm_dnet_linear_f32): srcs one tensor or up to three
+        (B, N, w_s) (or all (N, w_s)), weight (C_out, sum w_s) as nn.Linear stores it; the concatenation is never formed.  n_verts
+        (B) int32: rows behind a mesh's count are not read and come out as zeros."""
+        srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError("dnet_linear: one to three sources")
+        flat = srcs[0].dim() == 2
+        if flat:
+            srcs = [s.unsqueeze(0) for s in srcs]
+            resid = None if resid is None else resid.unsqueeze(0)
+        mats = [self._dnet_mat(s, "src") for s in srcs]
+        Bn, N = mats[0][0].shape[:2]
+        if any(m.shape[:2] != (Bn, N) for m, _ in mats):
+            raise ValueError("dnet_linear: the sources differ in their leading dimensions")
+        W, ldw = self._dnet_mat(weight, "weight")
+        if W.dim() != 2 or W.shape[1] != sum(m.shape[2] for m, _ in mats):
+            raise ValueError(f"dnet_linear: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
+        C_out = W.shape[0]
+        bias = None if bias is None else self._dev(bias, torch.float32, "bias")
+        if bias is not None and bias.shape != (C_out,):
+            raise ValueError("dnet_linear: bias must be (C_out,)")
+        R, ldr = (None, 0) if resid is None else self._dnet_mat(resid, "resid")
+        if R is not None and tuple(R.shape) != (Bn, N, C_out):
+            raise ValueError("dnet_linear: resid must have the shape of the output")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, C_out, "dnet_linear")
+        a = [(m, m.shape[2], ld) for m, ld in mats] + [(None, 0, 0)] * (3 - len(mats))
+        self._chk(self.lib.dm_dnet_linear_f32(self.ctx, Bn, N, C_out, len(mats), _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2],
+                                              _ptr(a[2][0]), a[2][1], a[2][2], _ptr(W), ldw, _ptr(bias), _ptr(R), ldr, 1 if relu else 0, _ptr(nv),
+                                              _ptr(out), ldo))
+        return out[0] if flat else out
+
+    def dnet_diffuse(self, x, mass, evals, evecs, times, n_verts=None, out=None):
+        """evecs (exp(-evals max(times, 1e-8)) * (evecs^T (mass * x))) (dm_dnet_diffuse_f32): x (B,N,C), mass (B,N), evals (B,K),
+        evecs (B,N,K), times (C); the spectrum stays on chip."""
+        X, ldx = self._dnet_mat(x, "x")
+        E, lde = self._dnet_mat(evecs, "evecs")
+        Bn, N, Cw = X.shape
+        K = E.shape[2]
+        mass = self._dev(mass, torch.float32, "mass")
+        evals = self._dev(evals, torch.float32, "evals")
+        times = self._dev(times, torch.float32, "times")
+        if tuple(E.shape[:2]) != (Bn, N) or tuple(mass.shape) != (Bn, N) or tuple(evals.shape) != (Bn, K) or tuple(times.shape) != (Cw,):
+            raise ValueError("dnet_diffuse: x (B,N,C), mass (B,N), evals (B,K), evecs (B,N,K), times (C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_diffuse")
+        self._chk(self.lib.dm_dnet_diffuse_f32(self.ctx, Bn, N, K, Cw, _ptr(X), ldx, _ptr(mass), _ptr(evals), _ptr(E), lde, _ptr(times), _ptr(nv),
+                                               _ptr(out), ldo))
+        return out
+
+    def dnet_gradient_features(self, x, row_len, cols, gx, gy, A_re, A_im=None, n_verts=None, out=None):
+        """tanh(gX * B_re + gY * B_im) of SpatialGradientFeatures (dm_dnet_gradfeat_f32) from the ELL rows of the gradient operators
+        (row_len (B,N) int32; cols int32, gx, gy float32 (B,N,nnz)) and x (B,N,C); A_im None: one matrix, no rotation."""
+        X, ldx = self._dnet_mat(x, "x")
+        Bn, N, Cw = X.shape
+        row_len = self._dev(row_len, torch.int32, "row_len")
+        cols = self._dev(cols, torch.int32, "cols")
+        gx = self._dev(gx, torch.float32, "gx")
+        gy = self._dev(gy, torch.float32, "gy")
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError("dnet_gradient_features: row_len (B,N), cols / gx / gy (B,N,nnz)")
+        Are, lda = self._dnet_mat(A_re, "A_re")
+        Aim = None
+        if A_im is not None:
+            Aim, lda2 = self._dnet_mat(A_im, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError("dnet_gradient_features: A_re / A_im must be (C, C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features")
+        self._chk(self.lib.dm_dnet_gradfeat_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
+                                                _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
+        return out
+
+    def diffusion_net_forward(self, weights, packed, x):
+        """A whole DiffusionNet (inference) on a padded batch: first_lin, per block diffuse -> gradient features -> the MLP (its first
+        layer reads (x, x_diffuse, x_grad) as three sources, its last adds the skip), last_lin.
+        weights  {"first": (W, b), "last": (W, b), "blocks": [{"times": t, "A_re": A or None, "A_im": A or None, "mlp": [(W, b), ...]}]},
+                 the module's parameters as they lie in memory (A_re None: no gradient features)
+        packed   fp32 padded operators with the attributes mass (B,N), evals (B,K), evecs (B,N,K), row_len, cols, gx, gy, n_verts_dev
+                 ((B) int32 or None when no mesh is padded) -- diffusion_net.layers.PackedOperators
+        x        (B, N, C_in), or up to three tensors read as concatenated along the channels.
+        Returns (B, N, C_out); rows behind a mesh's count are zero.  Intermediates live in buffers that the blocks share."""
+        nv = packed.n_verts_dev
+        W0, b0 = weights["first"]
+        cur = self.dnet_linear(x, W0, b0, n_verts=nv)
+        Bn, N, Cw = cur.shape
+        buf = lambda c=Cw: torch.empty((Bn, N, c), dtype=torch.float32, device=self.device)
+        nxt, xd, xg, hidden = buf(), buf(), None, {}
+        for blk in weights["blocks"]:
+            self.dnet_diffuse(cur, packed.mass, packed.evals, packed.evecs, blk["times"], n_verts=nv, out=xd)
+            src = [cur, xd]
+            if blk.get("A_re") is not None:
+                xg = buf() if xg is None else xg
+                self.dnet_gradient_features(xd, packed.row_len, packed.cols, packed.gx, packed.gy, blk["A_re"], blk.get("A_im"), n_verts=nv, out=xg)
+                src.append(xg)
+            mlp = blk["mlp"]
+            for i, (W, b) in enumerate(mlp):
+                if i + 1 == len(mlp):
+                    self.dnet_linear(src, W, b, resid=cur, n_verts=nv, out=nxt)
+                else:
+                    key = (i % 2, W.shape[0])
+                    if key not in hidden:
+                        hidden[key] = buf(W.shape[0])
+                    src = [self.dnet_linear(src, W, b, relu=True, n_verts=nv, out=hidden[key])]
+            cur, nxt = nxt, cur
+        W1, b1 = weights["last"]
+        return self.dnet_linear(cur, W1, b1, n_verts=nv)
+
     # ------------------------------------------------------------- heat-method geodesics (dm_heat_geodesic_*)
     _GEOD_INFO = ((1, "A + tW is not positive definite"),
                   (2, "the grounded stiffness matrix W is not positive definite (more than one connected component?)"),

@@ -495,6 +495,35 @@ int dm_dnet_rows(dm_ctx* ctx, int B, int N, int nt, const int32_t* tri, const do
 int dm_dnet_ell(dm_ctx* ctx, int B, int N, int nt, const void* rows, int nnz, const int32_t* n_verts /*nullable*/, double mass_eps, double shift,
                 int32_t* row_len, int32_t* ell_cols, double* l_vals, double* ell_vals, double* gx_vals, double* gy_vals, double* mass64, float* mass32);
 
+/* ---- DiffusionNet forward pass (inference) --------------------------------------------
+ * Replaces the network of diffusion_net/layers.py (LearnedTimeDiffusion with method 'spectral', SpatialGradientFeatures, MiniMLP,
+ * DiffusionNetBlock, first_lin / last_lin) for padded batches of B meshes with N vertices.  Every operand is fp32 and every product an
+ * fp32 fmaf chain on v_mfma_f32_32x32x2_f32 in ascending order of the contraction index: an output element depends on its own row and
+ * column of the operands only, so a mesh has the same bits alone and in any batch.  Matrix operands are row-major with a leading
+ * dimension (batch stride N * ld); no pointer needs more than 4-byte alignment.
+ *   dm_dnet_linear_f32    out[b,i,:] = act(concat(src_0[b,i,:w_0], .., src_{n_src-1}[b,i,:w]) W^T + bias) + resid[b,i,:]; W (C_out, sum w)
+ *                         as nn.Linear stores it; bias, resid nullable; act 0 none, 1 ReLU (applied before resid).  The concatenation
+ *                         is never formed.  Order: the chain over the concatenated index, then + bias, act, + resid.
+ *   dm_dnet_diffuse_f32   out = evecs (coef * (evecs^T (mass * x))), x (B,N,C), mass (B,N), evals (B,K), evecs (B,N,K), times (C);
+ *                         coef[k,c] = exp(-evals[k] max(times[c], 1e-8f)) evaluated in float64 and rounded once.  mass * x is rounded to
+ *                         fp32 (as the reference's expression), the sum over the vertices ascends, then the sum over k.  One workgroup
+ *                         per (mesh, 32 channels) keeps its K x 32 spectrum in LDS: K <= 1024.
+ *   dm_dnet_gradfeat_f32  gX = G_x x, gY = G_y x from ELL rows (row_len (B,N); cols, gx, gy (B,N,nnz): the layout of dm_dnet_ell in
+ *                         fp32), entries in stored order; B_re = gX A_re^T - gY A_im^T, B_im = gY A_re^T + gX A_im^T (A_im null:
+ *                         B_re = gX A_re^T, B_im = gY A_re^T); out = tanhf(gX * B_re + gY * B_im).  gX / gY are recomputed where a tile
+ *                         needs them and never stored.  A stored column outside [0, n_verts) contributes nothing.
+ * n_verts (device, nullable): rows i >= n_verts[b] are never read and are written as zeros; ELL slots q >= row_len[i] are never read.
+ * DM_EINVAL: B, N, C, K, nnz <= 0, a leading dimension below its width, a null operand, n_verts[b] outside [1, N] (read back: one
+ * stream synchronisation per call that passes n_verts). */
+int dm_dnet_linear_f32(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* src0, int w0, int ld0, const float* src1, int w1, int ld1,
+                       const float* src2, int w2, int ld2, const float* W, int ldw, const float* bias /*nullable*/, const float* resid /*nullable*/,
+                       int ldr, int act, const int32_t* n_verts /*nullable*/, float* out, int ldo);
+int dm_dnet_diffuse_f32(dm_ctx* ctx, int B, int N, int K, int C, const float* x, int ldx, const float* mass, const float* evals,
+                        const float* evecs, int lde, const float* times, const int32_t* n_verts /*nullable*/, float* out, int ldo);
+int dm_dnet_gradfeat_f32(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx, const float* gy,
+                         const float* x, int ldx, const float* A_re, const float* A_im /*nullable*/, int lda, const int32_t* n_verts /*nullable*/,
+                         float* out, int ldo);
+
 /* ---- heat-method geodesic distances ------------------------------------------------
  * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
  * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors
