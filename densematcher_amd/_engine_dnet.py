@@ -1,0 +1,257 @@
+"""
+MatchEngine, DiffusionNet: the operators of a batch of meshes and the fp32 forward pass.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from ._operands import pad_stack, ptr as _ptr
+
+
+class _DiffusionNetOps:
+    # ------------------------------------------------------------- DiffusionNet operators (dm_dnet_*)
+    def _dnet_assemble(self, V, F, normals):
+        """dm_dnet_rows + dm_dnet_ell of the meshes (V[b] (n_b, 3) float64, F[b] (m_b, 3) int32 NumPy arrays; normals: a list of
+        (n_b, 3) arrays or None), padded as laplacian_ell pads.  Returns the dict of device tensors."""
+        from .diffusion_net import _host
+        Bn = len(V)
+        n_verts = [int(v.shape[0]) for v in V]
+        N, nt = max(n_verts), max(int(f.shape[0]) for f in F)
+        # (through _dev: it refuses a call under another stream than the engine's, where the allocator could recycle the scratch below
+        #  while the context's stream still uses it)
+        tri_d = self._dev(pad_stack(F, (nt, 3), -1, np.int32), torch.int32, "tri")
+        vert_d = self._dev(pad_stack(V, (N, 3), 0.0, np.float64), torch.float64, "verts")
+        nrm_d = self._dev(pad_stack(normals, (N, 3), 0.0, np.float64), torch.float64, "normals") if normals is not None else None
+        nv_d = self._dev(np.asarray(n_verts, np.int32), torch.int32, "n_verts") if min(n_verts) < N else None
+        rows = torch.empty(int(self.lib.dm_dnet_rows_bytes(Bn, N, nt)), dtype=torch.uint8, device=self.device)
+        frames = torch.empty((Bn, N, 3, 3), dtype=torch.float64, device=self.device)
+        info = torch.empty((Bn,), dtype=torch.int32, device=self.device)
+        mx = C.c_int(0)
+        self._chk(self.lib.dm_dnet_rows(self.ctx, Bn, N, nt, _ptr(tri_d), _ptr(vert_d), _ptr(nrm_d), _ptr(nv_d), _host.DENOM_EPS, _host.GRAD_EPS,
+                                        _ptr(rows), _ptr(frames), _ptr(info), C.byref(mx)))
+        nnz = int(mx.value)
+        f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=self.device)
+        out = {"frames": frames, "info": info, "nnz": nnz, "n_verts": n_verts,
+               "row_len": torch.empty((Bn, N), dtype=torch.int32, device=self.device),
+               "cols": torch.empty((Bn, N, nnz), dtype=torch.int32, device=self.device),
+               "l": f64(Bn, N, nnz), "vals": f64(Bn, N, nnz), "gx": f64(Bn, N, nnz), "gy": f64(Bn, N, nnz), "mass64": f64(Bn, N),
+               "mass32": torch.empty((Bn, N), dtype=torch.float32, device=self.device)}
+        self._chk(self.lib.dm_dnet_ell(self.ctx, Bn, N, nt, _ptr(rows), nnz, _ptr(nv_d), _host.MASS_EPS, _host.MASS_EPS, _ptr(out["row_len"]),
+                                       _ptr(out["cols"]), _ptr(out["l"]), _ptr(out["vals"]), _ptr(out["gx"]), _ptr(out["gy"]), _ptr(out["mass64"]),
+                                       _ptr(out["mass32"])))
+        return out
+
+    def diffusion_operators(self, verts_list, faces_list, k_eig, normals=None):
+        """What diffusion_net.geometry.compute_operators precomputes (reference diffusion_net/geometry.py:275-391), for a batch of
+        meshes in one device call: dm_dnet_rows / dm_dnet_ell, then eigenbasis(ell=...) on M'^-1/2 (L + 1e-8 I) M'^-1/2.
+        verts_list / faces_list: (n_b, 3) / (m_b, 3) arrays; normals: None or a list with an (n_b, 3) array or None per mesh.
+        A mesh for which the device reports an undefined normal (bit 1 of info) gets its normals from the host -- the reference's
+        repair sequence, literally -- and runs again with them.
+        Returns a list with, per mesh, the dict frames (n,3,3), mass (n), row_len (n) int32, cols (n,nnz) int32, l / gx / gy (n,nnz),
+        evals (k), evecs (n,k): float64 tensors on the device, padding rows cut off, entries q < row_len[i] of row i real; and
+        info: the first pass's info word of the mesh."""
+        from .diffusion_net import _host
+        Bn = len(verts_list)
+        if Bn == 0:
+            return []
+        V = [np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64) for v in verts_list]
+        F = [np.ascontiguousarray(f.detach().cpu().numpy() if isinstance(f, torch.Tensor) else f) for f in faces_list]
+        for b in range(Bn):
+            if V[b].ndim != 2 or V[b].shape[1] != 3 or V[b].shape[0] == 0:
+                raise ValueError(f"diffusion_operators: mesh {b}: vertices must be (n, 3)")
+            if F[b].size == 0:
+                raise NotImplementedError("diffusion_operators: point clouds (no faces) are not built")
+            if F[b].ndim != 2 or F[b].shape[1] != 3 or F[b].min() < 0 or F[b].max() >= V[b].shape[0]:
+                raise ValueError(f"diffusion_operators: mesh {b}: faces must be (m, 3) indices into the {V[b].shape[0]} vertices")
+            F[b] = F[b].astype(np.int32)
+        given = [None] * Bn if normals is None else [None if g is None else np.asarray(g.detach().cpu().numpy() if isinstance(g, torch.Tensor) else g, np.float64)
+                                                      for g in normals]
+        have, lack = [b for b in range(Bn) if given[b] is not None], [b for b in range(Bn) if given[b] is None]
+        parts, first_info = [None] * Bn, [0] * Bn
+
+        def run(idx, nrm):
+            out = self._dnet_assemble([V[b] for b in idx], [F[b] for b in idx], nrm)
+            info = out["info"].cpu().numpy()
+            for q, b in enumerate(idx):
+                parts[b] = (out, q)
+                if nrm is None:
+                    first_info[b] = int(info[q])
+            return info
+
+        if lack:
+            info = run(lack, None)
+            redo = [b for q, b in enumerate(lack) if info[q] & 1]
+            for b in redo:
+                given[b] = _host.vertex_normals(V[b], F[b].astype(np.int64))
+            have = sorted(have + redo)
+        if have:
+            run(have, [given[b] for b in have])
+        res = [None] * Bn
+        groups = {}
+        for b in range(Bn):
+            groups.setdefault(id(parts[b][0]), []).append(b)
+        # eigenbasis() chooses between the filtered iteration and the dense route from the SMALLEST mesh of its batch (and the dense
+        # route takes at most 2048 padded vertices): meshes are solved with the partners that take the same route as they would alone,
+        # each group cut to its own largest mesh, so a small mesh neither drags a large one to the dense route nor changes its own
+        guard = next((g for g in range(12, 33) if (int(k_eig) + g) % 32 == 0), 32)
+        by_route = {}
+        for key, idx in groups.items():
+            for b in idx:
+                by_route.setdefault((key, 2 * (int(k_eig) + guard) > V[b].shape[0]), []).append(b)
+        for idx in by_route.values() if k_eig > 0 else groups.values():
+            out = parts[idx[0]][0]
+            if k_eig > 0:
+                sel = torch.as_tensor([parts[b][1] for b in idx], device=self.device)
+                Ng = max(V[b].shape[0] for b in idx)
+                cut = lambda t: t[sel, :Ng].contiguous()
+                out = {key: cut(out[key]) for key in ("frames", "mass64", "row_len", "cols", "l", "gx", "gy", "vals", "mass32")}
+                out["nnz"], out["n_verts"] = parts[idx[0]][0]["nnz"], [V[b].shape[0] for b in idx]
+                for q, b in enumerate(idx):
+                    parts[b] = (out, q)
+                ell = {"cols": out["cols"], "vals": out["vals"], "mass32": out["mass32"], "nnz": out["nnz"], "n_verts": out["n_verts"]}
+                lam, Phi, _, _ = self.eigenbasis(None, None, int(k_eig), guard=guard, ell=ell)
+                # dm_eigenbasis solves the problem of the fp32-rounded masses M' (Phi^T M' Phi = I).  The operators carry the float64
+                # masses M: Phi <- Phi (Phi^T M Phi)^-1/2, the symmetric orthonormalisation, with G = I + E, |E| ~ 1e-8:
+                # G^-1/2 = I - E/2 + 3/8 E^2 to 1e-24.  The eigenvalues move by E's second order; they stay as returned.
+                G = torch.matmul(Phi.transpose(1, 2), out["mass64"].unsqueeze(-1) * Phi)
+                E = G - torch.eye(G.shape[-1], dtype=G.dtype, device=G.device)
+                Phi = Phi - torch.matmul(Phi, 0.5 * E - 0.375 * torch.matmul(E, E))
+                lam = torch.clamp(lam, min=0.0)
+            for b in idx:
+                q, n = parts[b][1], V[b].shape[0]
+                res[b] = {"frames": out["frames"][q, :n], "mass": out["mass64"][q, :n], "row_len": out["row_len"][q, :n], "cols": out["cols"][q, :n],
+                          "l": out["l"][q, :n], "gx": out["gx"][q, :n], "gy": out["gy"][q, :n], "info": first_info[b],
+                          "evals": lam[q] if k_eig > 0 else torch.zeros((0,), dtype=torch.float64, device=self.device),
+                          "evecs": Phi[q, :n] if k_eig > 0 else torch.zeros((n, 0), dtype=torch.float64, device=self.device)}
+        return res
+
+    # ------------------------------------------------------------- DiffusionNet forward (dm_dnet_*_f32)
+    def _dnet_counts(self, n_verts, Bn):
+        if n_verts is None:
+            return None
+        nv = self._dev(n_verts, torch.int32, "n_verts")
+        if nv.shape != (Bn,):
+            raise ValueError(f"n_verts: expected {Bn} counts, got {tuple(nv.shape)}")
+        return nv
+
+    def _dnet_out(self, out, Bn, N, C, name):
+        if out is None:
+            return torch.empty((Bn, N, C), dtype=torch.float32, device=self.device), C
+        if out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != (Bn, N, C):
+            raise ValueError(f"{name}: out must be a float32 ({Bn}, {N}, {C}) tensor on {self.device}")
+        o, ld = self._strided(out, torch.float32, name)
+        if o is not out:
+            raise ValueError(f"{name}: out must have adjacent elements in a row and evenly spaced rows")
+        return out, ld
+
+    def dnet_linear(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None):
+        """out[b,i,:] = act(concat(srcs)[b,i,:] weight^T + bias) + resid[b,i,:] (dm_dnet_linear_f32): srcs one tensor or up to three
+        (B, N, w_s) (or all (N, w_s)), weight (C_out, sum w_s) as nn.Linear stores it; the concatenation is never formed.  n_verts
+        (B) int32: rows behind a mesh's count are not read and come out as zeros."""
+        srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError("dnet_linear: one to three sources")
+        flat = srcs[0].dim() == 2
+        if flat:
+            srcs = [s.unsqueeze(0) for s in srcs]
+            resid = None if resid is None else resid.unsqueeze(0)
+        mats = [self._strided(s, torch.float32, "src") for s in srcs]
+        Bn, N = mats[0][0].shape[:2]
+        if any(m.shape[:2] != (Bn, N) for m, _ in mats):
+            raise ValueError("dnet_linear: the sources differ in their leading dimensions")
+        W, ldw = self._strided(weight, torch.float32, "weight")
+        if W.dim() != 2 or W.shape[1] != sum(m.shape[2] for m, _ in mats):
+            raise ValueError(f"dnet_linear: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
+        C_out = W.shape[0]
+        bias = None if bias is None else self._dev(bias, torch.float32, "bias")
+        if bias is not None and bias.shape != (C_out,):
+            raise ValueError("dnet_linear: bias must be (C_out,)")
+        R, ldr = (None, 0) if resid is None else self._strided(resid, torch.float32, "resid")
+        if R is not None and tuple(R.shape) != (Bn, N, C_out):
+            raise ValueError("dnet_linear: resid must have the shape of the output")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, C_out, "dnet_linear")
+        a = [(m, m.shape[2], ld) for m, ld in mats] + [(None, 0, 0)] * (3 - len(mats))
+        self._chk(self.lib.dm_dnet_linear_f32(self.ctx, Bn, N, C_out, len(mats), _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2],
+                                              _ptr(a[2][0]), a[2][1], a[2][2], _ptr(W), ldw, _ptr(bias), _ptr(R), ldr, 1 if relu else 0, _ptr(nv),
+                                              _ptr(out), ldo))
+        return out[0] if flat else out
+
+    def dnet_diffuse(self, x, mass, evals, evecs, times, n_verts=None, out=None):
+        """evecs (exp(-evals max(times, 1e-8)) * (evecs^T (mass * x))) (dm_dnet_diffuse_f32): x (B,N,C), mass (B,N), evals (B,K),
+        evecs (B,N,K), times (C); the spectrum stays on chip."""
+        X, ldx = self._strided(x, torch.float32, "x")
+        E, lde = self._strided(evecs, torch.float32, "evecs")
+        Bn, N, Cw = X.shape
+        K = E.shape[2]
+        mass = self._dev(mass, torch.float32, "mass")
+        evals = self._dev(evals, torch.float32, "evals")
+        times = self._dev(times, torch.float32, "times")
+        if tuple(E.shape[:2]) != (Bn, N) or tuple(mass.shape) != (Bn, N) or tuple(evals.shape) != (Bn, K) or tuple(times.shape) != (Cw,):
+            raise ValueError("dnet_diffuse: x (B,N,C), mass (B,N), evals (B,K), evecs (B,N,K), times (C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_diffuse")
+        self._chk(self.lib.dm_dnet_diffuse_f32(self.ctx, Bn, N, K, Cw, _ptr(X), ldx, _ptr(mass), _ptr(evals), _ptr(E), lde, _ptr(times), _ptr(nv),
+                                               _ptr(out), ldo))
+        return out
+
+    def dnet_gradient_features(self, x, row_len, cols, gx, gy, A_re, A_im=None, n_verts=None, out=None):
+        """tanh(gX * B_re + gY * B_im) of SpatialGradientFeatures (dm_dnet_gradfeat_f32) from the ELL rows of the gradient operators
+        (row_len (B,N) int32; cols int32, gx, gy float32 (B,N,nnz)) and x (B,N,C); A_im None: one matrix, no rotation."""
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        row_len = self._dev(row_len, torch.int32, "row_len")
+        cols = self._dev(cols, torch.int32, "cols")
+        gx = self._dev(gx, torch.float32, "gx")
+        gy = self._dev(gy, torch.float32, "gy")
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError("dnet_gradient_features: row_len (B,N), cols / gx / gy (B,N,nnz)")
+        Are, lda = self._strided(A_re, torch.float32, "A_re")
+        Aim = None
+        if A_im is not None:
+            Aim, lda2 = self._strided(A_im, torch.float32, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError("dnet_gradient_features: A_re / A_im must be (C, C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features")
+        self._chk(self.lib.dm_dnet_gradfeat_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
+                                                _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
+        return out
+
+    def diffusion_net_forward(self, weights, packed, x):
+        """A whole DiffusionNet (inference) on a padded batch: first_lin, per block diffuse -> gradient features -> the MLP (its first
+        layer reads (x, x_diffuse, x_grad) as three sources, its last adds the skip), last_lin.
+        weights  {"first": (W, b), "last": (W, b), "blocks": [{"times": t, "A_re": A or None, "A_im": A or None, "mlp": [(W, b), ...]}]},
+                 the module's parameters as they lie in memory (A_re None: no gradient features)
+        packed   fp32 padded operators with the attributes mass (B,N), evals (B,K), evecs (B,N,K), row_len, cols, gx, gy, n_verts_dev
+                 ((B) int32 or None when no mesh is padded) -- diffusion_net.layers.PackedOperators
+        x        (B, N, C_in), or up to three tensors read as concatenated along the channels.
+        Returns (B, N, C_out); rows behind a mesh's count are zero.  Intermediates live in buffers that the blocks share."""
+        nv = packed.n_verts_dev
+        W0, b0 = weights["first"]
+        cur = self.dnet_linear(x, W0, b0, n_verts=nv)
+        Bn, N, Cw = cur.shape
+        buf = lambda c=Cw: torch.empty((Bn, N, c), dtype=torch.float32, device=self.device)
+        nxt, xd, xg, hidden = buf(), buf(), None, {}
+        for blk in weights["blocks"]:
+            self.dnet_diffuse(cur, packed.mass, packed.evals, packed.evecs, blk["times"], n_verts=nv, out=xd)
+            src = [cur, xd]
+            if blk.get("A_re") is not None:
+                xg = buf() if xg is None else xg
+                self.dnet_gradient_features(xd, packed.row_len, packed.cols, packed.gx, packed.gy, blk["A_re"], blk.get("A_im"), n_verts=nv, out=xg)
+                src.append(xg)
+            mlp = blk["mlp"]
+            for i, (W, b) in enumerate(mlp):
+                if i + 1 == len(mlp):
+                    self.dnet_linear(src, W, b, resid=cur, n_verts=nv, out=nxt)
+                else:
+                    key = (i % 2, W.shape[0])
+                    if key not in hidden:
+                        hidden[key] = buf(W.shape[0])
+                    src = [self.dnet_linear(src, W, b, relu=True, n_verts=nv, out=hidden[key])]
+            cur, nxt = nxt, cur
+        W1, b1 = weights["last"]
+        return self.dnet_linear(cur, W1, b1, n_verts=nv)
