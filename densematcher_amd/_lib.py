@@ -91,6 +91,8 @@ SIGNATURES = {
     "dm_spectral_signatures": (_i, [_p, _i, _i, _p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i, _p]),
     "dm_shape_diff_f64": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p]),
     "dm_pullback_forms_f64": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p]),
+    "dm_raster_pix2face": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _p, _p, _p, _p]),
+    "dm_lift_features": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

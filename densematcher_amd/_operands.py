@@ -145,3 +145,51 @@ def numpy_index(lst, n, who):
     if lo < -n or hi >= n:
         raise IndexError(f"{who}: index {lo if lo < -n else hi} is out of bounds for axis 0 with size {n}")
     return np.where(a < 0, a + n, a).astype(np.int32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# multi-view feature lifting: the one place where its meshes, cameras and given pix2face images are checked (MatchEngine on the
+# device route, projection.py on the host route)
+def to_numpy(a, dtype=None):
+    a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a if dtype is None else np.ascontiguousarray(a, dtype=dtype)
+
+
+def lift_mesh(verts, faces, who):
+    """(verts (n, 3) float64, faces (m, 3) int64) as NumPy arrays, every face index inside the mesh"""
+    V, F = to_numpy(verts, np.float64), to_numpy(faces)
+    if V.ndim != 2 or V.shape[1] != 3 or V.shape[0] == 0:
+        raise ValueError(f"{who}: vertices must be (n, 3)")
+    if F.ndim != 2 or F.shape[1] != 3 or F.shape[0] == 0 or not np.issubdtype(F.dtype, np.integer):
+        raise ValueError(f"{who}: faces must be (m, 3) integers")
+    if F.min() < 0 or F.max() >= V.shape[0]:
+        raise ValueError(f"{who}: faces must be (m, 3) indices into the {V.shape[0]} vertices")
+    return V, F.astype(np.int64)
+
+
+def lift_cameras(cameras, who, max_views=None):
+    """(R (views, 3, 3), T (views, 3)) float64 NumPy arrays"""
+    if cameras is None:
+        raise ValueError(f"{who}: cameras=(R, T) is required: the feature maps were rendered with some cameras, and the caller has them")
+    if len(cameras) != 2:
+        raise ValueError(f"{who}: cameras must be a pair (R (views, 3, 3), T (views, 3))")
+    R, T = to_numpy(cameras[0], np.float64), to_numpy(cameras[1], np.float64)
+    if R.ndim != 3 or R.shape[1:] != (3, 3) or T.shape != (R.shape[0], 3) or R.shape[0] == 0:
+        raise ValueError(f"{who}: cameras must be a pair (R (views, 3, 3), T (views, 3))")
+    if max_views is not None and R.shape[0] > max_views:
+        raise ValueError(f"{who}: at most {max_views} views per mesh")
+    return R, T
+
+
+def lift_pix2face(pix2face, views, n_faces, who):
+    """a given pix2face as an integer (views, H, H) tensor where it lies ((views, H, H, 1), pytorch3d's shape, is accepted), every
+    entry in [-1, n_faces): one read of (min, max), a single host round trip for a device tensor"""
+    g = pix2face if isinstance(pix2face, torch.Tensor) else torch.as_tensor(np.asarray(pix2face))
+    if g.dim() == 4 and g.shape[-1] == 1:
+        g = g[..., 0]
+    if g.dtype.is_floating_point or g.dtype == torch.bool or g.dim() != 3 or g.shape[0] != views or g.shape[1] != g.shape[2] or g.numel() == 0:
+        raise ValueError(f"{who}: pix2face must be ({views}, H, H) integers")
+    lo, hi = torch.stack(torch.aminmax(g)).tolist()
+    if lo < -1 or hi >= n_faces:
+        raise ValueError(f"{who}: pix2face holds {lo if lo < -1 else hi}: face indices must lie in [-1, {n_faces})")
+    return g

@@ -1,0 +1,147 @@
+"""
+densematcher.model of the reference: MeshFeaturizer, the module that turns a simplified mesh, its spectral operators and the per-view
+2D feature maps into normalised per-vertex descriptors (reference model.py:14-173).  extractor_3d and reconstructor are built as the
+reference builds them, so `model.extractor_3d.load_state_dict(...)` of the notebook loads with strict=True.
+
+The 2D half (rendering the textured mesh, the backbone, the upsampler) is outside this package: forward takes the per-view feature
+maps as fts= together with the cameras they were rendered with.  From there on -- back-projection (projection.get_features_per_vertex),
+positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
+route="device" (or "auto", see projection.AUTO_DEVICE and diffusion_net.layers.AUTO_DEVICE).
+"""
+import numpy as np
+import torch
+from torch import nn
+
+from . import diffusion_net
+from .diffusion_net.layers import PackedOperators
+from .projection import get_features_per_vertex, lift_features_many, mesh_arrays
+
+NORM_FLOOR = 1e-5
+
+
+def _reconstructor(layers, width, num_features, num_blocks):
+    """the head that maps the 3D features back to the 2D ones: layers = 1 one Linear, layers > 1 that many Linears with ReLU between
+    them (an nn.Sequential: the checkpoint's keys are its positions), layers = -1 a second DiffusionNet of the same depth"""
+    if layers == -1:
+        return diffusion_net.layers.DiffusionNet(C_in=width, C_out=num_features, C_width=width, N_block=num_blocks, dropout=True)
+    if layers == 1:
+        return nn.Linear(width, num_features)
+    hidden = [m for _ in range(layers - 1) for m in (nn.Linear(width, width), nn.ReLU())]
+    return nn.Sequential(*hidden, nn.Linear(width, num_features))
+
+
+class MeshFeaturizer(nn.Module):
+    def __init__(self, pretrained_upsampler_path=None, num_views=(3, 1), num_blocks=8, width=512, aggre_net_weights_folder=None,
+                 reconstructor_layers=1, num_encoding_functions=8, num_hks=16, *, num_features=768, extractor_2d=None):
+        """num_views: (num_azimuth, num_elevation) of the reference's camera placement; kept, the cameras come with every call.
+        pretrained_upsampler_path / aggre_net_weights_folder: kept for the reference's call signature, nothing is loaded from them.
+        extractor_2d: an optional 2D feature extractor (num_patches, featurizer.num_features); without one the width of the maps is
+        num_features and forward needs fts=."""
+        super().__init__()
+        self.pretrained_upsampler_path = pretrained_upsampler_path
+        self.extractor_2d = extractor_2d
+        if extractor_2d is not None:
+            num_features = extractor_2d.featurizer.num_features
+            self.H = self.W = extractor_2d.num_patches * 16
+        else:
+            self.H = self.W = None          # taken from the maps of a call
+        self.num_features = num_features
+        self.num_views = num_views
+        self.reconstructor_layers = reconstructor_layers
+        self.num_encoding_functions = num_encoding_functions
+        self.num_hks = num_hks
+        self.pos_enc_size = 3 * (2 * num_encoding_functions + 1)
+        self.diffusion_in_channels = num_features + self.num_hks + self.pos_enc_size
+        self.extractor_3d = diffusion_net.layers.DiffusionNet(C_in=self.diffusion_in_channels, C_out=width, C_width=width, N_block=num_blocks,
+                                                              dropout=True)
+        self.reconstructor = _reconstructor(reconstructor_layers, width, num_features, num_blocks)
+        self.use_lr_features = False
+
+    @property
+    def device(self):
+        return next(self.parameters()).device
+
+    def positional_encoding(self, tensor, include_input=True, log_sampling=True):
+        """[..., d] -> [..., d (2 n + 1)], n = num_encoding_functions: the input (include_input), then per frequency band sin and cos of
+        the input times the band; the bands are 2^0 .. 2^(n-1) (log_sampling) or n values spaced evenly between those two"""
+        n, d = self.num_encoding_functions, tensor.shape[-1]
+        if log_sampling:
+            bands = torch.exp2(torch.arange(n, dtype=tensor.dtype, device=tensor.device))
+        else:
+            bands = torch.linspace(1.0, 2.0 ** (n - 1), n, dtype=tensor.dtype, device=tensor.device)
+        phase = tensor.unsqueeze(-2) * bands.unsqueeze(-1)                                   # (..., n, d)
+        waves = torch.stack((torch.sin(phase), torch.cos(phase)), dim=-2)                   # (..., n, 2, d): band, then sin | cos
+        waves = waves.reshape(tensor.shape[:-1] + (2 * n * d,))
+        return torch.cat((tensor, waves), dim=-1) if include_input else waves
+
+    # ------------------------------------------------------------------ the neck
+    def _neck(self, verts, evals, evecs):
+        """(pos_enc (V, 51), hks (V, 16)) of a mesh: model.py:155,158"""
+        pos_enc = self.positional_encoding(verts * np.pi * 6)
+        hks = diffusion_net.geometry.compute_hks_autoscale(evals.contiguous(), evecs.contiguous(), self.num_hks)
+        return pos_enc, hks
+
+    @staticmethod
+    def _normalize(out_features):
+        return out_features / out_features.norm(dim=-1, keepdim=True).clamp(min=NORM_FLOOR)
+
+    def _verts(self, mesh_simp):
+        verts = mesh_arrays(mesh_simp)[0]
+        verts = verts if isinstance(verts, torch.Tensor) else torch.as_tensor(np.asarray(verts))
+        return verts.to(device=self.device, dtype=torch.float32)
+
+    def _need_maps(self, fts):
+        if fts is None and self.extractor_2d is None:
+            raise ValueError("MeshFeaturizer was built without extractor_2d: pass the per-view feature maps as fts=")
+
+    def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto"):
+        """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
+        and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
+        this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
+        rasteriser's.  route: 'host' (CPU raster, torch expressions), 'device' (HIP), 'auto'.
+        Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
+        self._need_maps(fts)
+        if route not in ("auto", "host", "device"):
+            raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
+        size = {} if self.H is None else {"H": self.H, "W": self.W}
+        if fts is not None:
+            size = {"H": fts.shape[2], "W": fts.shape[3]}
+        with torch.no_grad():
+            lifted = get_features_per_vertex(self.device, self.extractor_2d, mesh_raw, mesh_simp, self.num_views, ft_dim=self.num_features,
+                                             cameras=cameras, fts=fts, use_lr_features=self.use_lr_features, pix2face=pix2face, route=route, **size)
+        verts = self._verts(mesh_simp)
+        net_route = "torch" if route == "host" else route
+        if isinstance(operators, PackedOperators):
+            if len(operators.n_verts) != 1:
+                raise ValueError("forward takes one mesh: a PackedOperators of several meshes goes to forward_many")
+            packed = operators.to(self.device) if operators.device != self.device else operators
+            sources = (lifted,) + self._neck(verts, packed.evals[0], packed.evecs[0, :verts.shape[0]])
+            raw = self.extractor_3d(sources, route=net_route, operators=packed)
+        else:
+            ops = [None if op is None else op.to(self.device) for op in operators]       # frames, mass, L, evals, evecs, gradX, gradY
+            sources = (lifted,) + self._neck(verts, ops[3], ops[4])
+            raw = self.extractor_3d(sources, ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], route=net_route)
+        unit = self._normalize(raw)
+        return (unit, raw, lifted) if return_mvfeatures else unit
+
+    def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None):
+        """forward for a ragged list of meshes on the device: ONE batched lifting call and ONE batched DiffusionNet call.  packed: the
+        PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh."""
+        if fts_list is None:
+            self._need_maps(None)
+            raise NotImplementedError("rendering and the 2D backbone are outside this package: pass the per-view feature maps as fts_list=")
+        if not isinstance(packed, PackedOperators) or len(packed.n_verts) != len(meshes_simp):
+            raise ValueError("forward_many: packed must be the PackedOperators of the same meshes")
+        packed = packed.to(self.device) if packed.device != self.device else packed
+        with torch.no_grad():
+            mv = lift_features_many(fts_list, meshes_simp, cameras_list, pix2face_list, route="device", device=self.device)
+        xs = []
+        for b, mesh in enumerate(meshes_simp):
+            verts = self._verts(mesh)
+            if verts.shape[0] != packed.n_verts[b]:
+                raise ValueError(f"forward_many: mesh {b} has {verts.shape[0]} vertices, its packed operators {packed.n_verts[b]}")
+            xs.append((mv[b],) + self._neck(verts, packed.evals[b], packed.evecs[b, :verts.shape[0]]))
+        outs = self.extractor_3d.forward_many(xs, packed)
+        if return_mvfeatures:
+            return [(self._normalize(o), o, m) for o, m in zip(outs, mv)]
+        return [self._normalize(o) for o in outs]

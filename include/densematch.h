@@ -785,6 +785,37 @@ int dm_pullback_forms_f64(dm_ctx* ctx, int B, int N1, int N2, int k1, const int3
                           const int32_t* n_verts1 /*host, nullable*/, const int32_t* n_verts2 /*host, nullable*/,
                           const double* lam1 /*nullable*/, int ld_l1, double* Ga /*nullable*/, double* Gw /*nullable*/);
 
+/* ---- multi-view feature lifting -----------------------------------------------------
+ * The back-projection of get_features_per_vertex (reference densematcher/projection.py:27-130 with fts given; the simplified mesh's
+ * pix2face of render.py:31-53), for B meshes padded to N vertices and nt faces, each seen from up to `views` cameras
+ * (n_verts, n_views (B) int32 DEVICE, nullable = N / views).
+ *   Cameras: R (B,views,3,3), T (B,views,3) fp64 in the row-vector convention X_view = X_world R + T; x = focal X / Z, y = focal Y / Z
+ *   in NDC with +x left, +y up (the defaults of PerspectiveCameras, render.py:31).  Square images only (H == W).
+ *   dm_raster_pix2face  (projection.py:60-62,94-101)
+ *     proj (B,views,N,4) fp64 out: (x, y, Z, in-frame) per vertex, in-frame = 1 where -1 < x < 1 and -1 < y < 1 (projection.py:100).
+ *     pix2face (B,views,H,W) int32: the face nearest to the camera at the centre of pixel (r, c), x_c = 1 - (2c+1)/W, y_r = 1 - (2r+1)/H,
+ *       or -1.  A face is skipped when a vertex has Z <= 1e-6 or a non-finite projection, when |signed area| <= 1e-8, or when an index
+ *       lies outside [0, n_verts) (-1 pads tri).  A centre is inside where all three barycentric coordinates w_i / area are > 0; depth
+ *       z = 1 / sum b_i / Z_i in fp64, rounded to fp32 for the comparison; the smallest z wins, equal z goes to the lowest face index
+ *       (a 64-bit integer minimum over (depth bits << 32 | face): independent of the order of faces and workgroups).
+ *       given (B) int32 DEVICE, nullable: a mesh with given[b] != 0 keeps the pix2face the caller wrote (any rasteriser's; a face
+ *       index outside [0, nt) owns nothing) and only the marks below are made from it.
+ *     vis (B,views,N) bytes: 1 for every vertex of a face that owns a pixel (projection.py:94-97), else 0.
+ *   dm_lift_features  (projection.py:103-121)
+ *     maps (B,5) int64 DEVICE: per mesh the device address of its feature maps and their strides (view, channel, row, col) in
+ *     elements, f_dtype DM_F16 | DM_F32: NCHW and channels-last tensors are read where they lie.  For every vertex and every view
+ *     (ascending) with vis and in-frame set: grid_sample(ft, -(x, y), align_corners=True), bilinear, zero padding -- taps
+ *     ix = (1 - x)/2 (W-1), iy = (1 - y)/2 (H-1), fp32 weights, summed in the order nw, ne, sw, se; a tap outside the image is not
+ *     read.  out (B,N,ldo) fp32 = the sum over those views / their number, 0 where no view sees the vertex (projection.py:119-121)
+ *     and in rows past n_verts; count (B,N) int32, nullable: the number of views.  At most 64 views.  A vertex's bits depend on its
+ *     own mesh only: no floating-point atomics, no sums across workgroups. */
+int dm_raster_pix2face(dm_ctx* ctx, int B, int N, int nt, int views, int H, int W, const double* verts, const int32_t* tri,
+                       const int32_t* n_verts /*nullable*/, const double* R, const double* T, const int32_t* n_views /*nullable*/,
+                       double focal, const int32_t* given /*nullable*/, double* proj, int32_t* pix2face, unsigned char* vis);
+int dm_lift_features(dm_ctx* ctx, int B, int N, int views, int C, int H, int W, int f_dtype, const long long* maps,
+                     const double* proj, const unsigned char* vis, const int32_t* n_verts /*nullable*/,
+                     const int32_t* n_views /*nullable*/, float* out, int ldo, int32_t* count /*nullable*/);
+
 #ifdef __cplusplus
 }
 #endif
