@@ -17,6 +17,7 @@ DM_F16, DM_F32, DM_PROJECT_F64 = 0, 1, 0x10
 _p = C.c_void_p
 _i = C.c_int
 _d = C.c_double
+_ll = C.c_longlong
 
 # name -> (restype, argtypes); exactly the symbols include/densematch.h declares
 SIGNATURES = {
@@ -93,6 +94,8 @@ SIGNATURES = {
     "dm_pullback_forms_f64": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p]),
     "dm_raster_pix2face": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _p, _p, _p, _p]),
     "dm_lift_features": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "dm_jbu_filters_f32": (_i, [_p, _i, _i, _i, _p, _p, _p]),
+    "dm_jbu_apply": (_i, [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _i, _p, _ll, _ll, _ll, _ll]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

@@ -25,6 +25,7 @@ from . import _lib
 from ._engine_dnet import _DiffusionNetOps
 from ._engine_eval import _EvalOps
 from ._engine_geodesic import GraphTooWide, _GeodesicOps, heat_geodesic_check  # noqa: F401  (the mesh layer imports both from here)
+from ._engine_jbu import _JbuOps
 from ._engine_lift import _LiftOps
 from ._engine_mesh import _MeshOps
 from ._engine_network import _NetworkOps
@@ -35,7 +36,7 @@ class _KeepAlive(tuple):
     """an argument tuple that also holds the tensors its raw pointers refer to"""
 
 
-class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _EvalOps, _NetworkOps):
+class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _JbuOps, _EvalOps, _NetworkOps):
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MatchEngine needs a ROCm GPU (gfx950); there is no CPU fallback")

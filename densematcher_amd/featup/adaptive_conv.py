@@ -1,0 +1,46 @@
+"""
+featup.adaptive_conv_cuda of the reference: the per-pixel ("adaptive") convolution
+    out[b, c, y, x] = sum_{i, j} filters[b, y, x, i, j] * input[b, c, y + i, x + j]
+with input (B, C, H + I - 1, W + J - 1) already padded and filters (B, H, W, I, J).
+
+Routes:
+  torch    a loop over the I * J taps that accumulates shifted slices of the input in the reference kernel's order (i outer, j inner).
+           No (I J) x C x H x W buffer is formed (unfold would form one), autograd records it, it runs on any device: the training path.
+  device   inference on dm_jbu_apply -- which fuses the bicubic upsampling and the padding into the convolution -- is reached through
+           JBULearnedRange / JBUStack; a bare padded input has no device kernel of its own, so here 'device' is refused and 'auto' is
+           the torch route.
+"""
+import torch
+
+
+def _tap_loop(padded, filters):
+    B, C, Hp, Wp = padded.shape
+    _, H, W, I, J = filters.shape
+    out = None
+    for i in range(I):
+        for j in range(J):
+            term = filters[:, None, :, :, i, j] * padded[:, :, i:i + H, j:j + W]
+            out = term if out is None else out + term
+    return out
+
+
+def adaptive_conv(input, filters, route="auto"):
+    """input (B, C, H + I - 1, W + J - 1), filters (B, H, W, I, J) of the same dtype and device -> (B, C, H, W)"""
+    if route not in ("auto", "torch", "device"):
+        raise ValueError(f"route must be 'auto', 'torch' or 'device', not {route!r}")
+    if input.dim() != 4 or filters.dim() != 5 or filters.shape[0] != input.shape[0]:
+        raise ValueError("adaptive_conv: input (B, C, H + I - 1, W + J - 1) and filters (B, H, W, I, J)")
+    if input.shape[2] != filters.shape[1] + filters.shape[3] - 1 or input.shape[3] != filters.shape[2] + filters.shape[4] - 1:
+        raise ValueError(f"adaptive_conv: input {tuple(input.shape)} is not filters {tuple(filters.shape)} padded by the kernel size - 1")
+    if route == "device":
+        raise ValueError("adaptive_conv: the device kernel (dm_jbu_apply) upsamples and pads the source itself: use "
+                         "JBULearnedRange / JBUStack with route='device', or MatchEngine.jbu_apply")
+    return _tap_loop(input, filters)
+
+
+class AdaptiveConv:
+    """the reference's autograd.Function by its call: AdaptiveConv.apply(input, filters)"""
+
+    @staticmethod
+    def apply(input, filters):
+        return adaptive_conv(input, filters, route="torch")

@@ -3,8 +3,9 @@ densematcher.model of the reference: MeshFeaturizer, the module that turns a sim
 2D feature maps into normalised per-vertex descriptors (reference model.py:14-173).  extractor_3d and reconstructor are built as the
 reference builds them, so `model.extractor_3d.load_state_dict(...)` of the notebook loads with strict=True.
 
-The 2D half (rendering the textured mesh, the backbone, the upsampler) is outside this package: forward takes the per-view feature
-maps as fts= together with the cameras they were rendered with.  From there on -- back-projection (projection.get_features_per_vertex),
+The 2D half (rendering the textured mesh, the backbone) is outside this package: forward takes the per-view feature maps as fts=
+together with the cameras they were rendered with -- or, with an upsampler= (featup.upsamplers.JBUStack, extractor.load_upsampler),
+the backbone's low-resolution features fts_lr= and the images= they came from, which it upsamples 16x on the way into lifting.  From there on -- back-projection (projection.get_features_per_vertex),
 positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
 route="device" (or "auto", see projection.AUTO_DEVICE and diffusion_net.layers.AUTO_DEVICE).
 """
@@ -32,12 +33,17 @@ def _reconstructor(layers, width, num_features, num_blocks):
 
 class MeshFeaturizer(nn.Module):
     def __init__(self, pretrained_upsampler_path=None, num_views=(3, 1), num_blocks=8, width=512, aggre_net_weights_folder=None,
-                 reconstructor_layers=1, num_encoding_functions=8, num_hks=16, *, num_features=768, extractor_2d=None):
+                 reconstructor_layers=1, num_encoding_functions=8, num_hks=16, *, num_features=768, extractor_2d=None, upsampler=None,
+                 use_unitnorm=False, use_channelnorm=False):
         """num_views: (num_azimuth, num_elevation) of the reference's camera placement; kept, the cameras come with every call.
         pretrained_upsampler_path / aggre_net_weights_folder: kept for the reference's call signature, nothing is loaded from them.
         extractor_2d: an optional 2D feature extractor (num_patches, featurizer.num_features); without one the width of the maps is
-        num_features and forward needs fts=."""
+        num_features and forward needs fts=, or fts_lr= and images= when an upsampler is given.
+        upsampler: an optional JBUStack (a submodule: its parameters move and save with the model, under `upsampler.*`);
+        use_unitnorm / use_channelnorm: the normalisations of the low-resolution features in front of it (extractor.upsample_features)."""
         super().__init__()
+        self.upsampler = upsampler
+        self.use_unitnorm, self.use_channelnorm = use_unitnorm, use_channelnorm
         self.pretrained_upsampler_path = pretrained_upsampler_path
         self.extractor_2d = extractor_2d
         if extractor_2d is not None:
@@ -92,17 +98,32 @@ class MeshFeaturizer(nn.Module):
 
     def _need_maps(self, fts):
         if fts is None and self.extractor_2d is None:
-            raise ValueError("MeshFeaturizer was built without extractor_2d: pass the per-view feature maps as fts=")
+            raise ValueError("MeshFeaturizer was built without extractor_2d: pass the per-view feature maps as fts= (or, with an "
+                             "upsampler, the low-resolution features and their images as fts_lr= and images=)")
 
-    def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto"):
+    def _maps(self, fts, fts_lr, images, route):
+        """the per-view maps of a mesh: fts as given, else fts_lr (views, C, h, w) upsampled under images (views, 3, H, W)"""
+        if fts is not None or fts_lr is None:
+            return fts
+        if self.upsampler is None or images is None:
+            raise ValueError("fts_lr= needs a MeshFeaturizer built with upsampler= and the images the features came from as images=")
+        from .extractor import upsample_features
+        with torch.no_grad():
+            return upsample_features(self.upsampler, fts_lr.to(self.device), images.to(self.device), self.use_unitnorm, self.use_channelnorm,
+                                     route="torch" if route == "host" else route)
+
+    def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto", fts_lr=None,
+                images=None):
         """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
         and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
         this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
-        rasteriser's.  route: 'host' (CPU raster, torch expressions), 'device' (HIP), 'auto'.
+        rasteriser's.  route: 'host' (CPU raster, torch expressions), 'device' (HIP), 'auto'.  Without fts: fts_lr (views, C, h, w) and
+        images (views, 3, H, W) go through the upsampler (same route) and its maps straight into lifting.
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
-        self._need_maps(fts)
         if route not in ("auto", "host", "device"):
             raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
+        fts = self._maps(fts, fts_lr, images, route)
+        self._need_maps(fts)
         size = {} if self.H is None else {"H": self.H, "W": self.W}
         if fts is not None:
             size = {"H": fts.shape[2], "W": fts.shape[3]}
@@ -124,9 +145,15 @@ class MeshFeaturizer(nn.Module):
         unit = self._normalize(raw)
         return (unit, raw, lifted) if return_mvfeatures else unit
 
-    def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None):
+    def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None,
+                     fts_lr=None, images=None):
         """forward for a ragged list of meshes on the device: ONE batched lifting call and ONE batched DiffusionNet call.  packed: the
-        PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh."""
+        PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh.
+        Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device."""
+        if fts_list is None and fts_lr is not None:
+            if images is None or len(fts_lr) != len(meshes_simp) or len(images) != len(meshes_simp):
+                raise ValueError("forward_many: fts_lr= and images= are lists with one entry per mesh")
+            fts_list = [self._maps(None, f, i, "device") for f, i in zip(fts_lr, images)]
         if fts_list is None:
             self._need_maps(None)
             raise NotImplementedError("rendering and the 2D backbone are outside this package: pass the per-view feature maps as fts_list=")

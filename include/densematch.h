@@ -816,6 +816,36 @@ int dm_lift_features(dm_ctx* ctx, int B, int N, int views, int C, int H, int W, 
                      const double* proj, const unsigned char* vis, const int32_t* n_verts /*nullable*/,
                      const int32_t* n_views /*nullable*/, float* out, int ldo, int32_t* count /*nullable*/);
 
+/* ---- guided feature upsampling (FeatUp's JBU) -----------------------------------------
+ * One 2x stage of JBUStack (reference third_party/featup/featup/upsamplers.py:184-250, JBULearnedRange with guidance_dim 3, key_dim 32,
+ * radius 3, inference: the dropouts are identities), for B views.  The guidance is already pooled to the output size (H, W) = (2h, 2w).
+ *   dm_jbu_filters_f32  (upsamplers.py:213-243)
+ *     guidance (B,3,H,W) fp32, dense.  filters (B,H,W,49) fp32 out: per pixel the combined 7 x 7 kernel, tap t = 7 i + j at offset
+ *     (i - 3, j - 3): key = W2 gelu(W1 g + b1) + b2 per pixel (exact-erf GELU); logit_t = temp * <key(reflect(y+i-3), reflect(x+j-3)),
+ *     key(y, x)>; softmax over t with the maximum subtracted; times spatial_t; divided by max(sum, 1e-7); then
+ *     + 0.1 * (V2 gelu(V1 [kernel, g] + c1) + c2).  Everything fp32: fmaf chains in ascending index order starting from the bias; the
+ *     product of two keys as four chains over the channels 0, 1, 2, 3 mod 4, added as (s0 + s1) + (s2 + s3).
+ *     params: PACKED block of 6440 floats, offsets in floats:
+ *          0  W1 (32,3)      96  b1 (32)     128  W2 (32,32)    1152  b2 (32)                      range_proj.0 / range_proj.3
+ *       1184  V1 (49,52): columns 0..48 the kernel, 49..51 the guidance        3732  c1 (49)     fixup_proj.0
+ *       3784  V2 TRANSPOSED, (49 in, 52): row k holds V2[:, k], 3 floats of padding             6332  c2 (49)     fixup_proj.3
+ *       6384  spatial (49): get_spatial_kernel evaluated by the caller     6436  temp: exp(range_temp) clamped to [1e-4, 1e4]
+ *     The key map (B,H,W,32) fp32 is written once to the workspace and re-read.
+ *   dm_jbu_apply  (upsamplers.py:245-249)
+ *     out[b,c,y,x] = sum_{i,j} filters[b,y,x,7i+j] * P[b,c,y+i,x+j], an fp32 fmaf chain in the order i (outer), j (inner) starting from
+ *     zero, P = reflect_pad_3(bicubic_2x(src)) never stored: bicubic with align_corners=False, A = -0.75 and clamped indices; at exactly
+ *     2x the weights are (-0.03515625, 0.26171875, 0.87890625, -0.10546875) on texels k-2..k+1 for output 2k and the reverse on k-1..k+2
+ *     for 2k+1, applied along x first, then along y, each an fmaf chain over ascending texels.
+ *     src (B,C,h,w) fp16 | fp32 and out (B,C,2h,2w) fp32 | fp16 (rounded to nearest even) are addressed through ELEMENT strides (view,
+ *     channel, row, col): NCHW, channels-last and views of larger buffers are read and written where they lie.  No atomics; a
+ *     view's bits depend on that view alone.
+ * DM_EINVAL: H or W below 4 (h or w below 2), a null operand, a negative source stride, output strides that are not positive or that
+ * give two elements one address. */
+int dm_jbu_filters_f32(dm_ctx* ctx, int B, int H, int W, const float* guidance, const float* params, float* filters);
+int dm_jbu_apply(dm_ctx* ctx, int B, int C, int h, int w, int src_dtype, const void* src, long long s_view, long long s_chan,
+                 long long s_row, long long s_col, const float* filters, int out_dtype, void* out, long long o_view, long long o_chan,
+                 long long o_row, long long o_col);
+
 #ifdef __cplusplus
 }
 #endif
