@@ -96,6 +96,11 @@ SIGNATURES = {
     "dm_lift_features": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p]),
     "dm_jbu_filters_f32": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "dm_jbu_apply": (_i, [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _i, _p, _ll, _ll, _ll, _ll]),
+    "dm_agg_gather_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p, _i]),
+    "dm_groupnorm_stats_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p]),
+    "dm_groupnorm_relu_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i]),
+    "dm_conv3x3_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i]),
+    "dm_agg_mix_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, C.c_uint, _p, _p, _i]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._engine_aggre import _AggreOps
 from ._engine_dnet import _DiffusionNetOps
 from ._engine_eval import _EvalOps
 from ._engine_geodesic import GraphTooWide, _GeodesicOps, heat_geodesic_check  # noqa: F401  (the mesh layer imports both from here)
@@ -36,7 +37,7 @@ class _KeepAlive(tuple):
     """an argument tuple that also holds the tensors its raw pointers refer to"""
 
 
-class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _JbuOps, _EvalOps, _NetworkOps):
+class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _JbuOps, _AggreOps, _EvalOps, _NetworkOps):
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MatchEngine needs a ROCm GPU (gfx950); there is no CPU fallback")

@@ -1,13 +1,17 @@
 """
 densematcher.extractor of the reference, the part behind the 2D backbone (extractor.py:177-254): loading FeatUp's JBUStack from a
-released checkpoint, and the path from the backbone's low-resolution features to the per-view feature maps that lifting reads.  The
-backbone itself (SD / DINO, the aggregation network) and the image preprocessing are outside this package.
+released checkpoint, and the path from the backbone's low-resolution features to the per-view feature maps that lifting reads.  With
+load_aggre_net / features_from_backbone the path starts one stage earlier, at the raw outputs of the two frozen backbones (SD's s3, s4,
+s5 and DINO's tokens): the aggregation network (featurizers) runs here too.  The backbones themselves and the image preprocessing are
+outside this package.
 """
 import os
 import re
 
 import torch
 
+from .featurizers.SDDINO import aggregate_features
+from .featurizers.modules.projection_network import AggregationNetwork
 from .featup.layers import ChannelNorm, UnitNorm
 from .featup.upsamplers import get_upsampler
 
@@ -16,21 +20,24 @@ PREFIX = "upsampler."
 
 def parse_upsampler_name(path):
     """what the reference reads off the checkpoint's file name (extractor.py:185-195): {'imsize': int | None, 'channelnorm': bool,
-    'unitnorm': bool}; a missing flag is False, a missing size None"""
+    'unitnorm': bool, 'rotinv': bool}; a missing flag is False, a missing size None.  rotinv: the aggregation network was trained on
+    rotation-averaged features (features_from_backbone(rot_inv=True))."""
     name = os.fspath(path)
     size = re.search(r"imsize=(\d+)", name)
     flag = lambda key: (re.search(key + r"=(True|False)", name) or [None, "False"])[1] == "True"
-    return {"imsize": int(size.group(1)) if size else None, "channelnorm": flag("channelnorm"), "unitnorm": flag("unitnorm")}
+    return {"imsize": int(size.group(1)) if size else None, "channelnorm": flag("channelnorm"), "unitnorm": flag("unitnorm"),
+            "rotinv": flag("rotinv")}
 
 
 def load_upsampler(path_or_state_dict, num_features):
     """JBUStack(num_features) with the `upsampler.*` entries of a FeatUp checkpoint (extractor.py:206-212), loaded strict=True, in eval
     mode.  path_or_state_dict: the checkpoint file (a dict with 'state_dict', as released), such a dict, or a state_dict itself, with
-    or without the prefix.  Returns (upsampler, settings): settings = parse_upsampler_name(path) for a path, else {}."""
+    or without the prefix.  Returns (upsampler, settings): for a path the settings parse_upsampler_name reads that concern the upsampler
+    (imsize, channelnorm, unitnorm), else {}."""
     settings = {}
     state = path_or_state_dict
     if isinstance(state, (str, os.PathLike)):
-        settings = parse_upsampler_name(state)
+        settings = {k: v for k, v in parse_upsampler_name(state).items() if k != "rotinv"}
         state = torch.load(state, map_location="cpu")
     if "state_dict" in state and not isinstance(state["state_dict"], torch.Tensor):
         state = state["state_dict"]
@@ -53,3 +60,24 @@ def upsample_features(upsampler, features_lr, image, use_unitnorm=False, use_cha
     if hasattr(upsampler, "up1"):
         return upsampler(features_lr, image, route=route, **kwargs)
     return upsampler(features_lr, image)
+
+
+def load_aggre_net(path_or_state_dict, feature_dims=(640, 1280, 1280, 768), projection_dim=768, **kwargs):
+    """AggregationNetwork(feature_dims, projection_dim) with a released best_<size>.PTH (SDDINO.py:29-31), loaded by the reference's rule
+    (AggregationNetwork.load_pretrained_weights), in eval mode.  path_or_state_dict: the file or the state dict itself; kwargs: further constructor arguments."""
+    state = path_or_state_dict
+    if isinstance(state, (str, os.PathLike)):
+        state = torch.load(state, map_location="cpu")
+    net = AggregationNetwork(feature_dims=list(feature_dims), projection_dim=projection_dim, **kwargs)
+    net.load_pretrained_weights(state)
+    return net.eval()
+
+
+def features_from_backbone(aggre_net, upsampler, s3, s4, s5, dino, image, num_rotations=4, rot_inv=False, use_unitnorm=False,
+                           use_channelnorm=False, route="auto", **kwargs):
+    """SDDINOFeatureExtractor.forward behind the two backbone calls: s3, s4, s5 (SD's decoder features), dino (the ViT's tokens as a
+    (R B, C, P, P) view), R B images in rotation-major order with R = num_rotations when rot_inv, else 1 (featurizers.SDDINO.
+    aggregate_features), and image (B, 3, H, W), the unrotated normalised images -> features_hr (B, C, 16 P, 16 P).  route goes to both
+    stages, kwargs to upsample_features."""
+    features_lr = aggregate_features(aggre_net, s3, s4, s5, dino, num_rotations=num_rotations, rot_inv=rot_inv, route=route)
+    return upsample_features(upsampler, features_lr, image, use_unitnorm, use_channelnorm, route=route, **kwargs)

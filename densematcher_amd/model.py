@@ -5,7 +5,9 @@ reference builds them, so `model.extractor_3d.load_state_dict(...)` of the noteb
 
 The 2D half (rendering the textured mesh, the backbone) is outside this package: forward takes the per-view feature maps as fts=
 together with the cameras they were rendered with -- or, with an upsampler= (featup.upsamplers.JBUStack, extractor.load_upsampler),
-the backbone's low-resolution features fts_lr= and the images= they came from, which it upsamples 16x on the way into lifting.  From there on -- back-projection (projection.get_features_per_vertex),
+the backbone's low-resolution features fts_lr= and the images= they came from, which it upsamples 16x on the way into lifting; with
+an aggre_net= as well (featurizers.AggregationNetwork, extractor.load_aggre_net), the raw outputs of the two frozen backbones raw=
+(s3, s4, s5, dino).  From there on -- back-projection (projection.get_features_per_vertex),
 positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
 route="device" (or "auto", see projection.AUTO_DEVICE and diffusion_net.layers.AUTO_DEVICE).
 """
@@ -34,15 +36,19 @@ def _reconstructor(layers, width, num_features, num_blocks):
 class MeshFeaturizer(nn.Module):
     def __init__(self, pretrained_upsampler_path=None, num_views=(3, 1), num_blocks=8, width=512, aggre_net_weights_folder=None,
                  reconstructor_layers=1, num_encoding_functions=8, num_hks=16, *, num_features=768, extractor_2d=None, upsampler=None,
-                 use_unitnorm=False, use_channelnorm=False):
+                 use_unitnorm=False, use_channelnorm=False, aggre_net=None, rot_inv=False, num_rotations=4):
         """num_views: (num_azimuth, num_elevation) of the reference's camera placement; kept, the cameras come with every call.
         pretrained_upsampler_path / aggre_net_weights_folder: kept for the reference's call signature, nothing is loaded from them.
         extractor_2d: an optional 2D feature extractor (num_patches, featurizer.num_features); without one the width of the maps is
         num_features and forward needs fts=, or fts_lr= and images= when an upsampler is given.
         upsampler: an optional JBUStack (a submodule: its parameters move and save with the model, under `upsampler.*`);
-        use_unitnorm / use_channelnorm: the normalisations of the low-resolution features in front of it (extractor.upsample_features)."""
+        use_unitnorm / use_channelnorm: the normalisations of the low-resolution features in front of it (extractor.upsample_features).
+        aggre_net: an optional AggregationNetwork (a submodule, under `aggre_net.*`) for raw= calls; rot_inv / num_rotations: whether the
+        raw outputs hold num_rotations rotated copies per view (extractor.features_from_backbone)."""
         super().__init__()
         self.upsampler = upsampler
+        self.aggre_net = aggre_net
+        self.rot_inv, self.num_rotations = rot_inv, num_rotations
         self.use_unitnorm, self.use_channelnorm = use_unitnorm, use_channelnorm
         self.pretrained_upsampler_path = pretrained_upsampler_path
         self.extractor_2d = extractor_2d
@@ -101,8 +107,17 @@ class MeshFeaturizer(nn.Module):
             raise ValueError("MeshFeaturizer was built without extractor_2d: pass the per-view feature maps as fts= (or, with an "
                              "upsampler, the low-resolution features and their images as fts_lr= and images=)")
 
-    def _maps(self, fts, fts_lr, images, route):
-        """the per-view maps of a mesh: fts as given, else fts_lr (views, C, h, w) upsampled under images (views, 3, H, W)"""
+    def _maps(self, fts, fts_lr, images, route, raw=None):
+        """the per-view maps of a mesh: fts as given, else fts_lr (views, C, h, w) upsampled under images (views, 3, H, W), else raw
+        (s3, s4, s5, dino) through the aggregation network and the upsampler"""
+        if fts is None and fts_lr is None and raw is not None:
+            if self.aggre_net is None or self.upsampler is None or images is None:
+                raise ValueError("raw= needs a MeshFeaturizer built with aggre_net= and upsampler= and the images the features came from as images=")
+            from .extractor import features_from_backbone
+            with torch.no_grad():
+                return features_from_backbone(self.aggre_net, self.upsampler, *[t.to(self.device) for t in raw], images.to(self.device),
+                                              self.num_rotations, self.rot_inv, self.use_unitnorm, self.use_channelnorm,
+                                              route="torch" if route == "host" else route)
         if fts is not None or fts_lr is None:
             return fts
         if self.upsampler is None or images is None:
@@ -113,16 +128,17 @@ class MeshFeaturizer(nn.Module):
                                      route="torch" if route == "host" else route)
 
     def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto", fts_lr=None,
-                images=None):
+                images=None, raw=None):
         """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
         and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
         this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
         rasteriser's.  route: 'host' (CPU raster, torch expressions), 'device' (HIP), 'auto'.  Without fts: fts_lr (views, C, h, w) and
-        images (views, 3, H, W) go through the upsampler (same route) and its maps straight into lifting.
+        images (views, 3, H, W) go through the upsampler (same route) and its maps straight into lifting; or raw = (s3, s4, s5, dino), the
+        backbones' outputs for those images, through the aggregation network first.
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
         if route not in ("auto", "host", "device"):
             raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
-        fts = self._maps(fts, fts_lr, images, route)
+        fts = self._maps(fts, fts_lr, images, route, raw)
         self._need_maps(fts)
         size = {} if self.H is None else {"H": self.H, "W": self.W}
         if fts is not None:
@@ -146,10 +162,14 @@ class MeshFeaturizer(nn.Module):
         return (unit, raw, lifted) if return_mvfeatures else unit
 
     def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None,
-                     fts_lr=None, images=None):
+                     fts_lr=None, images=None, raw=None):
         """forward for a ragged list of meshes on the device: ONE batched lifting call and ONE batched DiffusionNet call.  packed: the
         PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh.
-        Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device."""
+        Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device; or raw, a list of (s3, s4, s5, dino) per mesh, through the aggregation network first."""
+        if fts_list is None and fts_lr is None and raw is not None:
+            if images is None or len(raw) != len(meshes_simp) or len(images) != len(meshes_simp):
+                raise ValueError("forward_many: raw= and images= are lists with one entry per mesh")
+            fts_list = [self._maps(None, None, i, "device", r) for r, i in zip(raw, images)]
         if fts_list is None and fts_lr is not None:
             if images is None or len(fts_lr) != len(meshes_simp) or len(images) != len(meshes_simp):
                 raise ValueError("forward_many: fts_lr= and images= are lists with one entry per mesh")

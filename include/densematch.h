@@ -846,6 +846,54 @@ int dm_jbu_apply(dm_ctx* ctx, int B, int C, int h, int w, int src_dtype, const v
                  long long s_row, long long s_col, const float* filters, int out_dtype, void* out, long long o_view, long long o_chan,
                  long long o_row, long long o_col);
 
+/* ---- aggregation network of the 2D backbone --------------------------------------------
+ * The part of the reference between the raw outputs of the frozen backbones and features_lr (densematcher/featurizers/SDDINO.py:53-57,
+ * 67-90; modules/projection_network.py:89-123; modules/resnet.py:271-287), inference.  Everything fp32 on rows = pixels, channels
+ * last: L levels and B images lie as (L, B, npix, C) with a leading dimension, npix = P_h * P_w, pixel p = y * P_w + x.  The 1x1
+ * convolutions are dm_dnet_linear_f32.  No atomics; an image has the same bits alone and in any batch.
+ *   dm_agg_gather_f32  (SDDINO.py:53-57, 76-88)
+ *     n_src <= 8 sources src0 .. (the rest null), each of R * B images in the order r * B + b, read where they lie.  desc HOST
+ *     (n_src, 8) int64: C_s, h_s, w_s, the element strides (image, channel, row, col) and the dtype DM_F16 | DM_F32 of source s.
+ *     out (B, npix, ld) fp32: out[b, p, off_s + c] = (sum over r ascending of rot_{-r step}(interp_s(src_s[r B + b, c]))(p)) / R with
+ *     off_s the summed widths of the sources in front; the sum starts from zero, the division is a true division.
+ *     interp: F.interpolate(bilinear, align_corners=False) to (P_h, P_w) -- source coordinate max(0, (t + 1/2) h_s / P_h - 1/2) in
+ *     fp64, weights rounded to fp32, (1-ly)((1-lx) a + lx b) + ly((1-lx) c + lx d); the identity when the sizes agree.
+ *     rot_angle: output pixel (y, x) samples at ix = cos xb - sin yb + P_w/2 - 1/2, iy = sin xb + cos yb + P_h/2 - 1/2,
+ *     xb = x - P_w/2 + 1/2, yb = y - P_h/2 + 1/2, theta = radians(angle) (torchvision's rotate: positive angles turn counter-clockwise),
+ *     bilinear with zero padding: coordinates in fp64, weights in fp32, taps in the order nw, ne, sw, se, a tap outside the map is not
+ *     read.  r = 0 or step_deg = 0 takes the pixel itself.  R = 1, step_deg = 0 is the concatenation laid out as rows.
+ *   dm_groupnorm_stats_f32
+ *     per (image, group) over the npix * C/G values x[img, :, g C/G .. (g+1) C/G): the fp64 sum, then the fp64 sum of squared
+ *     deviations from the fp64 mean -- two passes, each thread's elements ascending, the 256 partial sums through a fixed tree --
+ *     biased variance, rstd = 1 / sqrt(var + 1e-5); mean, rstd (n_img, G) fp32, each rounded once.
+ *   dm_groupnorm_relu_f32
+ *     out[img, p, c] = max(0, fmaf((x - mean) * rstd, gamma[level, c], beta[level, c])), level = img / B; gamma, beta (n_img / B, C).
+ *   dm_conv3x3_f32
+ *     3 x 3, stride 1, zero padding 1, x (L, B, P_h, P_w, C_in) -> out (L, B, P_h, P_w, C_out); w (L, C_out, 9 C_in) with contraction
+ *     index k = (3 dy + dx) C_in + c for the input at (y + dy - 1, x + dx - 1, c).  An exact fp32 fmaf chain over ascending k starting
+ *     from zero (v_mfma_f32_32x32x2_f32, like dm_dnet_linear_f32); a tap outside the image contributes nothing.
+ *   dm_agg_mix_f32
+ *     out[b, p, c] = sum over l ascending of mix[l] * max(0, GN3(y3[l, b, p, c]) + GNs(ys[l, b, p, c])), GN as in dm_groupnorm_relu_f32
+ *     with the statistics (L * B, G) and affine parameters (L, C) of each branch; the first term is assigned, the rest are added, every
+ *     product and sum rounded on its own.  y3, ys (L, B, npix, ld); mix (L) fp32; out (B, npix, ldo).  identity_mask, bit l: level l
+ *     has no shortcut convolution (a block with as many channels in as out, resnet.py:280-283): ys[l] holds the block's input and is
+ *     added as it is.  L <= 32.
+ * DM_EINVAL: a size that is not positive, C not a multiple of G, a leading dimension below its width, a null operand, a negative
+ * stride, R > 16, more than 8 sources, more than 32 levels. */
+int dm_agg_gather_f32(dm_ctx* ctx, int n_src, const long long* desc, const void* src0, const void* src1 /*nullable*/,
+                      const void* src2 /*nullable*/, const void* src3 /*nullable*/, const void* src4 /*nullable*/,
+                      const void* src5 /*nullable*/, const void* src6 /*nullable*/, const void* src7 /*nullable*/, int R, int B, int P_h,
+                      int P_w, double step_deg, float* out, int ld);
+int dm_groupnorm_stats_f32(dm_ctx* ctx, int n_img, int npix, int C, int G, const float* x, int ld, float* mean, float* rstd);
+int dm_groupnorm_relu_f32(dm_ctx* ctx, int n_img, int B, int npix, int C, int G, const float* x, int ldx, const float* mean,
+                          const float* rstd, const float* gamma, const float* beta, float* out, int ldo);
+int dm_conv3x3_f32(dm_ctx* ctx, int L, int B, int P_h, int P_w, int C_in, int C_out, const float* x, int ldx, const float* w,
+                   float* out, int ldo);
+int dm_agg_mix_f32(dm_ctx* ctx, int L, int B, int npix, int C, int G, const float* y3, int ld3, const float* ys, int lds,
+                   const float* mean3, const float* rstd3, const float* gamma3, const float* beta3, const float* means,
+                   const float* rstds, const float* gammas, const float* betas, unsigned identity_mask, const float* mix, float* out,
+                   int ldo);
+
 #ifdef __cplusplus
 }
 #endif
