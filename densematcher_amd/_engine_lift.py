@@ -25,7 +25,7 @@ class _LiftOps:
             V.append(v), F.append(f.astype(np.int32)), R.append(r), T.append(t)
         n_verts, n_views = [v.shape[0] for v in V], [r.shape[0] for r in R]
         N, nt, Vw = max(n_verts), max(f.shape[0] for f in F), max(n_views)
-        m = {"B": Bn, "N": N, "nt": nt, "Vw": Vw, "n_verts": n_verts, "n_views": n_views, "n_faces": [f.shape[0] for f in F],
+        m = {"B": Bn, "N": N, "nt": nt, "Vw": Vw, "n_verts": n_verts, "n_views": n_views, "n_faces": [f.shape[0] for f in F], "host": (V, F, R, T),
              "verts": self._dev(pad_stack(V, (N, 3), 0.0, np.float64), torch.float64, "verts"),
              "tri": self._dev(pad_stack(F, (nt, 3), -1, np.int32), torch.int32, "tri"),
              "R": self._dev(pad_stack(R, (Vw, 3, 3), 0.0, np.float64), torch.float64, "R"),

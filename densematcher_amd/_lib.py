@@ -94,6 +94,7 @@ SIGNATURES = {
     "dm_pullback_forms_f64": (_i, [_p, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p]),
     "dm_raster_pix2face": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _p, _p, _p, _p]),
     "dm_lift_features": (_i, [_p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "dm_render_phong": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
     "dm_jbu_filters_f32": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "dm_jbu_apply": (_i, [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _i, _p, _ll, _ll, _ll, _ll]),
     "dm_agg_gather_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p, _i]),

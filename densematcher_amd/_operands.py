@@ -193,3 +193,74 @@ def lift_pix2face(pix2face, views, n_faces, who):
     if lo < -1 or hi >= n_faces:
         raise ValueError(f"{who}: pix2face holds {lo if lo < -1 else hi}: face indices must lie in [-1, {n_faces})")
     return g
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# textured-mesh rendering: the one place where its textures, colours and lights are checked (MatchEngine.render_phong on the device
+# route, render.py on the host route)
+def _tensor(a):
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+def render_texture(tex, n_verts, n_faces, who):
+    """A mesh's texture: None (white), ("vertex", colours (n, 3)) or ("uv", map (Ht, Wt, 3), verts_uvs (n_uv, 2), faces_uvs (m, 3)).
+    Returns (0,), (1, colours fp32 tensor) or (2, map fp32 tensor, verts_uvs fp32 tensor, faces_uvs int32 array), the tensors where
+    they lie; every UV index inside verts_uvs."""
+    if tex is None:
+        return (0,)
+    if not isinstance(tex, (tuple, list)) or not tex or tex[0] not in ("vertex", "uv"):
+        raise ValueError(f"{who}: a texture is None, ('vertex', colours) or ('uv', map, verts_uvs, faces_uvs)")
+    if tex[0] == "vertex":
+        if len(tex) != 2:
+            raise ValueError(f"{who}: a vertex texture is ('vertex', colours)")
+        col = _tensor(tex[1])
+        if col.dim() != 2 or tuple(col.shape) != (n_verts, 3):
+            raise ValueError(f"{who}: vertex colours must be ({n_verts}, 3): one RGB row per vertex")
+        return 1, col.to(torch.float32).contiguous()
+    if len(tex) != 4:
+        raise ValueError(f"{who}: a UV texture is ('uv', map, verts_uvs, faces_uvs)")
+    tmap, uvs, fuv = _tensor(tex[1]), _tensor(tex[2]), to_numpy(tex[3])
+    if tmap.dim() != 3 or tmap.shape[2] != 3 or tmap.shape[0] == 0 or tmap.shape[1] == 0 or max(tmap.shape[:2]) > 32768:
+        raise ValueError(f"{who}: a texture map must be (Ht, Wt, 3), at most 32768 x 32768")
+    if uvs.dim() != 2 or uvs.shape[1] != 2 or uvs.shape[0] == 0:
+        raise ValueError(f"{who}: verts_uvs must be (n_uv, 2)")
+    if fuv.shape != (n_faces, 3) or not np.issubdtype(fuv.dtype, np.integer):
+        raise ValueError(f"{who}: faces_uvs must be ({n_faces}, 3) integers: one row per face")
+    if fuv.min() < 0 or fuv.max() >= uvs.shape[0]:
+        raise ValueError(f"{who}: faces_uvs must be ({n_faces}, 3) indices into the {uvs.shape[0]} rows of verts_uvs")
+    return 2, tmap.to(torch.float32).contiguous(), uvs.to(torch.float32).contiguous(), np.ascontiguousarray(fuv, np.int32)
+
+
+def render_corners(F, n):
+    """the faces incident to every vertex as a CSR (ptr (n + 1,), face (3 m,)) int32: one entry per corner, ascending face index"""
+    flat = np.asarray(F, np.int64).ravel()
+    face = (np.argsort(flat, kind="stable") // 3).astype(np.int32)
+    ptr = np.concatenate(([0], np.cumsum(np.bincount(flat, minlength=n)))).astype(np.int32)
+    return ptr, face
+
+
+def render_colour(c, who, name):
+    a = np.asarray(to_numpy(c), np.float64).reshape(-1)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError(f"{who}: {name} must be three finite numbers")
+    return a.astype(np.float32)
+
+
+def render_points(p, views, who, name):
+    """optional per-view points (views, 3) (or one (3,) / (1, 3) point for every view) as float64"""
+    if p is None:
+        return None
+    a = to_numpy(p, np.float64)
+    a = np.broadcast_to(a.reshape(-1, 3), (views, 3)) if a.size == 3 else a
+    if a.shape != (views, 3) or not np.isfinite(a).all():
+        raise ValueError(f"{who}: {name} must be ({views}, 3) finite numbers")
+    return np.ascontiguousarray(a)
+
+
+def render_normals(nrm, n_verts, who):
+    if nrm is None:
+        return None
+    a = to_numpy(nrm, np.float64)
+    if a.shape != (n_verts, 3) or not np.isfinite(a).all():
+        raise ValueError(f"{who}: vertex normals must be ({n_verts}, 3) finite numbers")
+    return a

@@ -3,11 +3,12 @@ densematcher.model of the reference: MeshFeaturizer, the module that turns a sim
 2D feature maps into normalised per-vertex descriptors (reference model.py:14-173).  extractor_3d and reconstructor are built as the
 reference builds them, so `model.extractor_3d.load_state_dict(...)` of the notebook loads with strict=True.
 
-The 2D half (rendering the textured mesh, the backbone) is outside this package: forward takes the per-view feature maps as fts=
+The 2D backbone is outside this package: forward takes the per-view feature maps as fts=
 together with the cameras they were rendered with -- or, with an upsampler= (featup.upsamplers.JBUStack, extractor.load_upsampler),
 the backbone's low-resolution features fts_lr= and the images= they came from, which it upsamples 16x on the way into lifting; with
 an aggre_net= as well (featurizers.AggregationNetwork, extractor.load_aggre_net), the raw outputs of the two frozen backbones raw=
-(s3, s4, s5, dino).  From there on -- back-projection (projection.get_features_per_vertex),
+(s3, s4, s5, dino); or a backbone= callable, images (views, 3, H, W) -> (s3, s4, s5, dino), for the views of mesh_raw that render.py
+renders here.  From there on -- back-projection (projection.get_features_per_vertex),
 positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
 route="device" (or "auto", see projection.AUTO_DEVICE and diffusion_net.layers.AUTO_DEVICE).
 """
@@ -127,17 +128,33 @@ class MeshFeaturizer(nn.Module):
             return upsample_features(self.upsampler, fts_lr.to(self.device), images.to(self.device), self.use_unitnorm, self.use_channelnorm,
                                      route="torch" if route == "host" else route)
 
+    def _render_views(self, meshes_raw, cameras_list, route, image_size):
+        """the views of the raw meshes for a backbone: per mesh the RGB planes (views, 3, H, W) fp32 and the cameras (R, T) they were
+        rendered with (generated from num_views around the origin where None, as the reference's get_features_per_vertex does)"""
+        from .render import render_many
+        size = int(image_size or self.H or 512)
+        outs = render_many(self.device, meshes_raw, self.num_views, size, size, cameras_list, [torch.zeros((1, 3))] * len(meshes_raw), route=route,
+                           planes=torch.float32)
+        return [o[5] for o in outs], [(o[1].R, o[1].T) for o in outs]
+
     def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto", fts_lr=None,
-                images=None, raw=None):
+                images=None, raw=None, backbone=None, image_size=None):
         """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
         and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
         this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
         rasteriser's.  route: 'host' (CPU raster, torch expressions), 'device' (HIP), 'auto'.  Without fts: fts_lr (views, C, h, w) and
         images (views, 3, H, W) go through the upsampler (same route) and its maps straight into lifting; or raw = (s3, s4, s5, dino), the
-        backbones' outputs for those images, through the aggregation network first.
+        backbones' outputs for those images, through the aggregation network first.  With none of fts / fts_lr / raw and a backbone=
+        (images (views, 3, H, W) -> (s3, s4, s5, dino)): mesh_raw (verts_list / faces_list, optional .textures) is rendered with
+        `cameras` (generated from num_views when None) at image_size (default: the extractor's size, else 512), the images go to the
+        backbone and the result takes the raw= route with images=.
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
         if route not in ("auto", "host", "device"):
             raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
+        if fts is None and fts_lr is None and raw is None and backbone is not None:
+            with torch.no_grad():
+                (images,), (cameras,) = self._render_views([mesh_raw], [cameras], route, image_size)
+                raw = backbone(images)
         fts = self._maps(fts, fts_lr, images, route, raw)
         self._need_maps(fts)
         size = {} if self.H is None else {"H": self.H, "W": self.W}
@@ -162,10 +179,15 @@ class MeshFeaturizer(nn.Module):
         return (unit, raw, lifted) if return_mvfeatures else unit
 
     def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None,
-                     fts_lr=None, images=None, raw=None):
+                     fts_lr=None, images=None, raw=None, backbone=None, image_size=None):
         """forward for a ragged list of meshes on the device: ONE batched lifting call and ONE batched DiffusionNet call.  packed: the
         PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh.
-        Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device; or raw, a list of (s3, s4, s5, dino) per mesh, through the aggregation network first."""
+        Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device; or raw, a list of (s3, s4, s5, dino) per mesh, through the aggregation network first;
+        or backbone=, as in forward: the raw meshes are rendered in ONE device call (cameras_list entries may be None)."""
+        if fts_list is None and fts_lr is None and raw is None and backbone is not None:
+            with torch.no_grad():
+                images, cameras_list = self._render_views(list(meshes_raw), list(cameras_list), "device", image_size)
+                raw = [backbone(i) for i in images]
         if fts_list is None and fts_lr is None and raw is not None:
             if images is None or len(raw) != len(meshes_simp) or len(images) != len(meshes_simp):
                 raise ValueError("forward_many: raw= and images= are lists with one entry per mesh")

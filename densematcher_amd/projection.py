@@ -1,7 +1,7 @@
 """
 densematcher.projection of the reference: get_features_per_vertex, the back-projection of per-view 2D feature maps onto the vertices
-of the simplified mesh (reference projection.py:27-130), with the feature maps GIVEN (fts=).  Rendering the textured mesh and the 2D
-backbone are outside this package; the caller has the maps and the cameras they were rendered with.
+of the simplified mesh (reference projection.py:27-130), with the feature maps GIVEN (fts=) or made from the rendered views of the raw
+mesh (render.py) by a callable extractor=.  The 2D backbone itself is outside this package.
 
 What the reference takes from pytorch3d is restated here ('Multi-view feature lifting'):
   cameras     (R (views,3,3), T (views,3)), row vectors: X_view = X_world R + T; PerspectiveCameras' defaults: focal length 1, principal
@@ -210,17 +210,27 @@ def rasterize_visibility(mesh_simp, cameras, H, W, route="auto", focal_length=1.
 
 def get_features_per_vertex(device, extractor, mesh, mesh_simp, num_views, ft_dim=768, H=512, W=512, cameras=None, center=torch.zeros((1, 3)),
                             dummy_testing=False, render_dir=None, fts=None, use_lr_features=False, *, pix2face=None, route="auto"):
-    """The reference's get_features_per_vertex (projection.py:27-130) with the feature maps given: fts (views, C, H, W), cameras =
-    (R (views,3,3), T (views,3)), mesh_simp the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair).
-    Returns ft_per_vertex (V, C) fp32 on `device`: the mean of the bilinear samples over the views that see a vertex, zeros where no
-    view does.  No normalisation is applied.
-    extractor, mesh (the raw mesh), num_views, center, render_dir and use_lr_features belong to the rendering half and are not read.
-    ft_dim, H and W are the reference's width of the result and size of its renders: here the width and the size -- of the maps and of
-    the raster alike -- are those of fts, so these three are not read either, beyond H == W.  pix2face: see the top of this file."""
+    """The reference's get_features_per_vertex (projection.py:27-130).  mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0],
+    or a (verts, faces) pair).  Returns ft_per_vertex (V, C) fp32 on `device`: the mean of the bilinear samples over the views that see
+    a vertex, zeros where no view does.  No normalisation is applied.
+    With fts (views, C, H, W) given, cameras = (R (views,3,3), T (views,3)) are those the maps were rendered with; extractor, mesh (the
+    raw mesh), num_views, center and use_lr_features are not read, and the width and the size -- of the maps and of the raster alike --
+    are those of fts (ft_dim, H and W are not read beyond H == W).
+    With fts=None and a callable extractor the function does what the reference does: `mesh` (raw, textured) is rendered at H x W
+    (render.batch_render; cameras=None generates them from num_views and center), extractor(batched_renderings[idx][..., :3]) gives
+    (ft_hr, ft_lr) per view, (1, C, h, w) each, of which use_lr_features picks one; mesh_simp is rasterised with the same cameras at the
+    maps' size and the maps are lifted.  render_dir is not read.  pix2face: see the top of this file."""
     who = "get_features_per_vertex"
     if dummy_testing:
         raise NotImplementedError(f"{who}: dummy_testing is not built")
     if fts is None:
-        raise NotImplementedError(f"{who}: rendering and the 2D backbone are outside this package: pass the per-view feature maps as fts=")
+        if not callable(extractor):
+            raise NotImplementedError(f"{who}: the 2D backbone is outside this package: pass the per-view feature maps as fts=, or an "
+                                      "extractor= that maps a rendered (H, W, 3) view to (ft_hr, ft_lr)")
+        from .render import batch_render
+        renders, camera, _, _, _ = batch_render(device, mesh, num_views, H, W, cameras, center, route=route)
+        cameras = (camera.R, camera.T)
+        maps = [extractor(renders[idx][..., :3])[1 if use_lr_features else 0] for idx in range(len(renders))]
+        fts = torch.cat([ft if ft.dim() == 4 else ft[None] for ft in maps])
     _check_square(H, W, who)
     return lift_features_many([fts], [mesh_simp], [cameras], None if pix2face is None else [pix2face], route=route, device=device)[0]

@@ -816,6 +816,38 @@ int dm_lift_features(dm_ctx* ctx, int B, int N, int views, int C, int H, int W, 
                      const double* proj, const unsigned char* vis, const int32_t* n_verts /*nullable*/,
                      const int32_t* n_views /*nullable*/, float* out, int ldo, int32_t* count /*nullable*/);
 
+/* ---- textured-mesh rendering ----------------------------------------------------------
+ * The hard-Phong views of the raw, textured meshes (reference densematcher/render.py:13-54: pytorch3d's MeshRasterizer with
+ * blur_radius 0 and one face per pixel, HardPhongShader, one point light per view, default Materials and BlendParams), for B meshes
+ * padded to N vertices and nt faces, each seen from up to `views` <= 64 cameras.  Cameras, pixel centres, the face-skipping rule and
+ * ownership are those of dm_raster_pix2face above (the same projection and key-image kernels).  This library's restatement of
+ * pytorch3d's defaults, not pinned against pytorch3d:
+ *   normals (B,N,3) fp64, in/out: s / max(|s|, 1e-6) with s = the sum over the incident faces, in ascending face order, of
+ *     cross(v1 - v0, v2 - v0).  inc_ptr (B,N+1), inc_face (B,n_inc) int32: per vertex the faces of its corners (CSR, one entry per
+ *     corner, ascending; entries outside [0, nt) are skipped).  normals_given (B) int32, nullable: a mesh with normals_given[b] != 0
+ *     keeps the normals the caller wrote.
+ *   per covered pixel: the owner's screen-space barycentrics b_i (the raster's expressions) are perspective-corrected in fp64,
+ *     b'_i = (b_i / Z_i) / sum_j (b_j / Z_j), and rounded to fp32; position p, normal n (normalised again, eps 1e-6) and texel are
+ *     b'-interpolated in fp32.
+ *   tex (B,8) int64 DEVICE per mesh: kind (0 none = white, 1 vertex colours, 2 UV map), the address of the colours (n,3) fp32 or of the
+ *     map (Ht,Wt,3) fp32, Ht (kind 1: the number of colour rows), Wt, the address of verts_uvs (n_uv,2) fp32, of faces_uvs (n_fuv,3)
+ *     int32, n_uv, n_fuv.  UV: the sample position x = u (Wt-1), y = (1-v)(Ht-1) is clamped to the map; four taps nw, ne, sw, se
+ *     (grid_sample of the row-flipped map at 2 uv - 1, bilinear, align_corners, border padding).  A face or UV index outside its
+ *     array leaves the texel white.
+ *   light (B,views,3) fp64, nullable = the camera centre C = -T R^T.  l = unit(L - p), cos = n.l, v = unit(C - p), r = -l + 2 cos n,
+ *     alpha = relu(v.r) [cos > 0]; rgb = (ambient + diffuse relu(cos)) texel + specular alpha^shininess, unit(a) = a / max(|a|, 1e-6).
+ *     shade (HOST, 13 floats): ambient, diffuse, specular, background (3 each), shininess.
+ *   rgba (B,views,H,W,4) fp32: (rgb, 1) on covered pixels, (background, 0) elsewhere and in views past n_views; no clamping.
+ *   zbuf (B,views,H,W) fp32: 1 / sum b_i / Z_i, the fp32 value of the key, -1 on background.  pix2face (B,views,H,W) int32, -1 on
+ *     background.  planes (B,views,3,H,W), nullable, p_dtype DM_F16 | DM_F32: the RGB planes in the backbone's layout.
+ * No floating-point atomics; a mesh's bits do not depend on what shares the call. */
+int dm_render_phong(dm_ctx* ctx, int B, int N, int nt, int views, int H, int W, const double* verts, const int32_t* tri,
+                    const int32_t* n_verts /*nullable*/, const double* R, const double* T, const int32_t* n_views /*nullable*/,
+                    double focal, const int32_t* inc_ptr, const int32_t* inc_face, int n_inc,
+                    const int32_t* normals_given /*nullable*/, double* normals, const long long* tex,
+                    const double* light /*nullable*/, const float* shade /*host, 13*/, float* rgba, float* zbuf,
+                    int32_t* pix2face, void* planes /*nullable*/, int p_dtype);
+
 /* ---- guided feature upsampling (FeatUp's JBU) -----------------------------------------
  * One 2x stage of JBUStack (reference third_party/featup/featup/upsamplers.py:184-250, JBULearnedRange with guidance_dim 3, key_dim 32,
  * radius 3, inference: the dropouts are identities), for B views.  The guidance is already pooled to the output size (H, W) = (2h, 2w).
