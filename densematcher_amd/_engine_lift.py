@@ -6,7 +6,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._operands import lift_cameras, lift_mesh, lift_pix2face, pad_stack, ptr as _ptr
+from ._operands import image_frame, lift_cameras, lift_mesh, lift_pix2face, pad_stack, ptr as _ptr
 
 MAX_VIEWS = 64
 
@@ -36,13 +36,7 @@ class _LiftOps:
 
     def _lift_raster(self, m, H, W, focal_length, pix2face_list, who):
         """dm_raster_pix2face on the meshes m: (proj (B,Vw,N,4), pix2face (B,Vw,H,W), vis (B,Vw,N) uint8)"""
-        H, W = int(H), int(W)
-        if H != W:
-            raise ValueError(f"{who}: square images only (H = {H}, W = {W})")
-        if H <= 0:
-            raise ValueError(f"{who}: H and W must be positive")
-        if not (float(focal_length) > 0.0 and np.isfinite(float(focal_length))):
-            raise ValueError(f"{who}: the focal length must be positive and finite")
+        H, W = image_frame(H, W, focal_length, who)
         Bn, N, Vw = m["B"], m["N"], m["Vw"]
         p2f = torch.full((Bn, Vw, H, W), -1, dtype=torch.int32, device=self.device)
         given = None

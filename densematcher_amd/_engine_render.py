@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._operands import (host_ptr, pad_stack, ptr as _ptr, render_colour, render_corners, render_normals, render_points, render_texture)
+from ._operands import (host_ptr, image_frame, pad_stack, ptr as _ptr, render_colour, render_corners, render_normals, render_points, render_texture)
 
 AMBIENT, DIFFUSE, SPECULAR, BACKGROUND, SHININESS = (0.6, 0.6, 0.6), (0.4, 0.4, 0.5), (0.01, 0.01, 0.01), (1.0, 1.0, 1.0), 64.0
 
@@ -37,13 +37,7 @@ class _RenderOps:
         who = "render_phong"
         m = self._lift_meshes(verts_list, faces_list, cameras_list, who)
         Bn, N, nt, Vw = m["B"], m["N"], m["nt"], m["Vw"]
-        H, W = int(H), int(W)
-        if H != W:
-            raise ValueError(f"{who}: square images only (H = {H}, W = {W})")
-        if H <= 0:
-            raise ValueError(f"{who}: H and W must be positive")
-        if not (float(focal_length) > 0.0 and np.isfinite(float(focal_length))):
-            raise ValueError(f"{who}: the focal length must be positive and finite")
+        H, W = image_frame(H, W, focal_length, who)
         if planes not in (None, torch.float32, torch.float16):
             raise ValueError(f"{who}: planes must be None, torch.float32 or torch.float16")
         for name, lst in (("textures_list", textures_list), ("normals_list", normals_list), ("light_list", light_list)):

@@ -155,6 +155,17 @@ def to_numpy(a, dtype=None):
     return a if dtype is None else np.ascontiguousarray(a, dtype=dtype)
 
 
+def image_frame(H, W, focal_length, who):
+    """(H, W) as ints of a square, non-empty image; focal_length (None: the caller has none to check) positive and finite"""
+    if int(H) != int(W):
+        raise ValueError(f"{who}: square images only (H = {H}, W = {W})")
+    if int(H) <= 0:
+        raise ValueError(f"{who}: H and W must be positive")
+    if focal_length is not None and not (float(focal_length) > 0.0 and np.isfinite(float(focal_length))):
+        raise ValueError(f"{who}: the focal length must be positive and finite")
+    return int(H), int(W)
+
+
 def lift_mesh(verts, faces, who):
     """(verts (n, 3) float64, faces (m, 3) int64) as NumPy arrays, every face index inside the mesh"""
     V, F = to_numpy(verts, np.float64), to_numpy(faces)

@@ -24,6 +24,7 @@ import scipy.sparse
 import torch
 
 from . import _host, utils
+from .. import _routes
 from .utils import toNP
 
 
@@ -72,24 +73,6 @@ def build_grad(verts, edges, edge_tangent_vectors):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-def _device_engine():
-    if not torch.cuda.is_available():
-        return None
-    from ..engine import default_engine
-    return default_engine()
-
-
-def _pick_route(route):
-    if route not in ("auto", "host", "device"):
-        raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
-    if route == "host":
-        return None
-    eng = _device_engine()
-    if eng is None and route == "device":
-        raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-    return eng
-
-
 def _ell_to_coo(n, row_len, cols, vals, device, dtype):
     """rows in ELL (entries q < row_len[i] of row i, sorted by column) -> coalesced torch COO, rounded once to dtype"""
     keep = torch.arange(cols.shape[1], device=cols.device)[None, :] < row_len[:, None]
@@ -123,11 +106,11 @@ def _from_host(verts, faces, k_eig, normals):
 def _compute_many(verts_list, faces_list, k_eig, normals, route):
     for f in faces_list:
         _no_clouds(f)
-    eng = _pick_route(route)
+    picked = _routes.pick_host(route)                  # "auto": the device when a GPU is present
     nrm = [None] * len(verts_list) if normals is None else list(normals)
-    if eng is None:
+    if picked != "device":
         return [_from_host(v, f, k_eig, g) for v, f, g in zip(verts_list, faces_list, nrm)]
-    ops = eng.diffusion_operators(verts_list, faces_list, k_eig, normals=None if normals is None else nrm)
+    ops = _routes.engine_or_none().diffusion_operators(verts_list, faces_list, k_eig, normals=None if normals is None else nrm)
     return [_from_device(op, v.device, v.dtype) for op, v in zip(ops, verts_list)]
 
 

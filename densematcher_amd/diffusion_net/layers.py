@@ -19,6 +19,7 @@ Not built on the device: training / backward, implicit_dense, point clouds (thei
 import torch
 import torch.nn as nn
 
+from .. import _routes
 from .geometry import from_basis, to_basis
 
 # where tools/dnet_forward_time.py measured the device route faster than the torch route on an MI355X (README.md):
@@ -298,21 +299,7 @@ class DiffusionNet(nn.Module):
             return "the input and the parameters must be float32"
         if any(not p.is_cuda for p in params):
             return "the parameters must be on the GPU"
-        if torch.is_grad_enabled() and any(t.requires_grad for t in list(xs) + params + [t for t in extra if isinstance(t, torch.Tensor)]):
-            return "a tensor requires grad (the device route records no autograd graph: call under torch.no_grad())"
-        return None
-
-    def _pick(self, route, xs, extra, batch):
-        if route not in ("auto", "torch", "device"):
-            raise ValueError(f"route must be 'auto', 'torch' or 'device', not {route!r}")
-        if route == "torch":
-            return "torch"
-        why = self._device_obstacle(xs, extra)
-        if route == "device":
-            if why is not None:
-                raise RuntimeError("DiffusionNet route='device': " + why)
-            return "device"
-        return "device" if why is None and AUTO_DEVICE["batch" if batch else "single"] else "torch"
+        return _routes.grad_obstacle(list(xs) + params + [t for t in extra if isinstance(t, torch.Tensor)])
 
     def _tail(self, x, mass, edges, faces):
         if self.outputs_at == "vertices":
@@ -360,7 +347,8 @@ class DiffusionNet(nn.Module):
             up = lambda t: None if t is None else t.unsqueeze(0)
             xs = [x.unsqueeze(0) for x in xs]
             mass, L, evals, evecs, gradX, gradY, edges, faces = (up(t) for t in (mass, L, evals, evecs, gradX, gradY, edges, faces))
-        picked = self._pick(route, xs, (mass, evals, evecs), xs[0].shape[0] > 1)
+        picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs)),
+                                    AUTO_DEVICE["batch" if xs[0].shape[0] > 1 else "single"], refusal=RuntimeError)
         self.last_route = picked
         if picked == "torch":
             if mass is None or (self.diffusion_method == "spectral" and (evals is None or evecs is None)):

@@ -12,6 +12,8 @@ Routes:
 """
 import torch
 
+from .. import _routes
+
 
 def _tap_loop(padded, filters):
     B, C, Hp, Wp = padded.shape
@@ -26,8 +28,7 @@ def _tap_loop(padded, filters):
 
 def adaptive_conv(input, filters, route="auto"):
     """input (B, C, H + I - 1, W + J - 1), filters (B, H, W, I, J) of the same dtype and device -> (B, C, H, W)"""
-    if route not in ("auto", "torch", "device"):
-        raise ValueError(f"route must be 'auto', 'torch' or 'device', not {route!r}")
+    _routes.check(route, _routes.TORCH)
     if input.dim() != 4 or filters.dim() != 5 or filters.shape[0] != input.shape[0]:
         raise ValueError("adaptive_conv: input (B, C, H + I - 1, W + J - 1) and filters (B, H, W, I, J)")
     if input.shape[2] != filters.shape[1] + filters.shape[3] - 1 or input.shape[3] != filters.shape[2] + filters.shape[4] - 1:

@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from .. import _routes
 from .adaptive_conv import adaptive_conv
 
 # where tools/jbu_time.py measured the device route not slower than the torch route of the same process on an MI355X (README.md,
@@ -30,36 +31,19 @@ PB_RP_W1, PB_RP_B1, PB_RP_W2, PB_RP_B2, PB_FX_W1, PB_FX_B1, PB_FX_W2T, PB_FX_B2,
     0, 96, 128, 1152, 1184, 3732, 3784, 6332, 6384, 6436, 6440)
 
 
-def _engine():
-    if not torch.cuda.is_available():
-        return None
-    from ..engine import default_engine
-    return default_engine()
-
-
-def _obstacle(module, source, guidance):
+def _obstacle(module, source, guidance, shape_obstacle):
     """why the device route cannot run this call, or None"""
+    if shape_obstacle:
+        return shape_obstacle
     if module.training:
         return "the module is in training mode (the device route is inference only: call .eval())"
-    if torch.is_grad_enabled() and any(t.requires_grad for t in [source, guidance] + list(module.parameters())):
-        return "a tensor requires grad (the device route records no autograd graph: call under torch.no_grad())"
-    return None
+    return _routes.grad_obstacle([source, guidance] + list(module.parameters()))
 
 
-def _pick(module, route, source, guidance, kind, shape_obstacle=None):
-    if route not in ("auto", "torch", "device"):
-        raise ValueError(f"route must be 'auto', 'torch' or 'device', not {route!r}")
-    if route == "torch":
-        return "torch"
-    why = shape_obstacle or _obstacle(module, source, guidance)
-    if route == "device":
-        if why is not None:
-            raise ValueError(f"{type(module).__name__} route='device': {why}")
-        if _engine() is None:
-            raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-        return "device"
-    on_gpu = source.is_cuda and guidance.is_cuda and all(p.is_cuda for p in module.parameters())
-    return "device" if why is None and on_gpu and AUTO_DEVICE[kind] and _engine() is not None else "torch"
+def _route_of(module, route, source, guidance, kind, shape_obstacle):
+    """what both modules hand to the one picker: "torch" or "device" for this call"""
+    return _routes.pick_torch(route, type(module).__name__, lambda: _obstacle(module, source, guidance, shape_obstacle), AUTO_DEVICE[kind],
+                              lambda: source.is_cuda and guidance.is_cuda and all(p.is_cuda for p in module.parameters()))
 
 
 class JBULearnedRange(nn.Module):
@@ -147,9 +131,9 @@ class JBULearnedRange(nn.Module):
         """source (B, C, h, w), guidance (B, 3, H, W) -> (B, C, H, W)"""
         if source.shape[0] != guidance.shape[0]:
             raise ValueError("source and guidance differ in their batch size")
-        if _pick(self, route, source, guidance, "stage", self._shape_obstacle(source, guidance)) == "torch":
+        if _route_of(self, route, source, guidance, "stage", self._shape_obstacle(source, guidance)) == "torch":
             return self._forward_torch(source, guidance)
-        eng = _engine()
+        eng = _routes.engine_or_none()
         return eng.jbu_apply(source, eng.jbu_filters(guidance, self.packed(eng.device)))
 
 
@@ -195,13 +179,13 @@ class JBUStack(nn.Module):
         if source.shape[0] != guidance.shape[0]:
             raise ValueError("source and guidance differ in their batch size")
         shape_obstacle = None if min(source.shape[2:]) >= 2 else "the source must be at least 2 x 2"
-        if _pick(self, route, source, guidance, "stack", shape_obstacle) == "torch":
+        if _route_of(self, route, source, guidance, "stack", shape_obstacle) == "torch":
             x = source
             for up in (self.up1, self.up2, self.up3, self.up4):
                 x = self.upsample(x, guidance, up, route="torch")
             y = self.fixup_proj(x) * 0.1 + x
         else:
-            eng = _engine()
+            eng = _routes.engine_or_none()
             y = eng.jbu_stack(self.packed(eng.device), source, guidance, chunk=chunk)
         if out_dtype is not None or memory_format is not None:
             y = y.to(dtype=out_dtype or y.dtype, memory_format=memory_format or torch.preserve_format)

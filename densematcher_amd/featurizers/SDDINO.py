@@ -11,6 +11,7 @@ AggregationNetwork.forward decides.
 import torch
 import torch.nn.functional as F
 
+from .. import _routes
 from .modules import projection_network as pn
 from .util import rotate
 
@@ -35,8 +36,8 @@ def aggregate_features(aggre_net, s3, s4, s5, dino, num_rotations=1, rot_inv=Fal
     if tuple(dino.shape[2:]) != size:
         raise ValueError(f"aggregate_features: dino {tuple(dino.shape[2:])} is not on s3's patch grid {size}")
     step = 360.0 / R if rot_inv else 0.0
-    if pn.pick_route(aggre_net, route, (s3, s4, s5, dino)) == "device":
-        eng = pn.engine()
+    if pn.route_of(aggre_net, route, (s3, s4, s5, dino)) == "device":
+        eng = _routes.engine_or_none()
         rows = eng.agg_gather([s3, s4, s5, dino], num_rotations=R, step_deg=step, size=size)
         return eng.aggregate(aggre_net.packed(eng.device), rows, *size)
     gathered = gather_features(s3.float(), s4.float(), s5.float(), dino.float())

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from ... import _routes
 from .resnet import BottleneckBlock, ResNet
 
 # whether tools/aggre_time.py measured the device route faster than the torch route of the same process on an MI355X (README.md,
@@ -25,30 +26,11 @@ from .resnet import BottleneckBlock, ResNet
 AUTO_DEVICE = True
 
 
-def engine():
-    if not torch.cuda.is_available():
-        return None
-    from ...engine import default_engine
-    return default_engine()
-
-
-def pick_route(module, route, tensors):
-    """'torch' or 'device' for a call of `module` (an AggregationNetwork) on `tensors`"""
-    if route not in ("auto", "torch", "device"):
-        raise ValueError(f"route must be 'auto', 'torch' or 'device', not {route!r}")
-    if route == "torch":
-        return "torch"
-    why = module.device_obstacle()
-    if why is None and torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + list(module.parameters())):
-        why = "a tensor requires grad (the device route records no autograd graph: call under torch.no_grad())"
-    if route == "device":
-        if why is not None:
-            raise ValueError(f"AggregationNetwork route='device': {why}")
-        if engine() is None:
-            raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-        return "device"
-    on_gpu = all(t.is_cuda for t in tensors) and all(p.is_cuda for p in module.parameters())
-    return "device" if why is None and on_gpu and AUTO_DEVICE and engine() is not None else "torch"
+def route_of(module, route, tensors):
+    """'torch' or 'device' for a call of `module` (an AggregationNetwork) on `tensors`: what it hands to the one picker"""
+    operands = lambda: list(tensors) + list(module.parameters())
+    return _routes.pick_torch(route, "AggregationNetwork", lambda: module.device_obstacle() or _routes.grad_obstacle(operands()), AUTO_DEVICE,
+                              lambda: all(t.is_cuda for t in operands()))
 
 
 class PackedAggre:
@@ -165,8 +147,8 @@ class AggregationNetwork(nn.Module):
     def forward(self, batch, pose=None, route="auto"):
         """batch (B, sum feature_dims, H, W): the levels' features side by side -> (B, projection_dim, H, W); on the device route
         NCHW-shaped over channels-last memory.  pose is not read (the reference's signature)."""
-        if pick_route(self, route, (batch,)) == "torch":
+        if route_of(self, route, (batch,)) == "torch":
             return self._forward_torch(batch)
-        eng = engine()
+        eng = _routes.engine_or_none()
         rows = eng.agg_gather([batch])
         return eng.aggregate(self.packed(eng.device), rows, batch.shape[2], batch.shape[3])

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import diffusion_net
+from . import _routes, diffusion_net
 from .diffusion_net.layers import PackedOperators
 from .projection import get_features_per_vertex, lift_features_many, mesh_arrays
 
@@ -118,7 +118,7 @@ class MeshFeaturizer(nn.Module):
             with torch.no_grad():
                 return features_from_backbone(self.aggre_net, self.upsampler, *[t.to(self.device) for t in raw], images.to(self.device),
                                               self.num_rotations, self.rot_inv, self.use_unitnorm, self.use_channelnorm,
-                                              route="torch" if route == "host" else route)
+                                              route=_routes.torch_route(route))
         if fts is not None or fts_lr is None:
             return fts
         if self.upsampler is None or images is None:
@@ -126,7 +126,7 @@ class MeshFeaturizer(nn.Module):
         from .extractor import upsample_features
         with torch.no_grad():
             return upsample_features(self.upsampler, fts_lr.to(self.device), images.to(self.device), self.use_unitnorm, self.use_channelnorm,
-                                     route="torch" if route == "host" else route)
+                                     route=_routes.torch_route(route))
 
     def _render_views(self, meshes_raw, cameras_list, route, image_size):
         """the views of the raw meshes for a backbone: per mesh the RGB planes (views, 3, H, W) fp32 and the cameras (R, T) they were
@@ -149,8 +149,7 @@ class MeshFeaturizer(nn.Module):
         `cameras` (generated from num_views when None) at image_size (default: the extractor's size, else 512), the images go to the
         backbone and the result takes the raw= route with images=.
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
-        if route not in ("auto", "host", "device"):
-            raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
+        _routes.check(route, _routes.HOST)
         if fts is None and fts_lr is None and raw is None and backbone is not None:
             with torch.no_grad():
                 (images,), (cameras,) = self._render_views([mesh_raw], [cameras], route, image_size)
@@ -164,7 +163,7 @@ class MeshFeaturizer(nn.Module):
             lifted = get_features_per_vertex(self.device, self.extractor_2d, mesh_raw, mesh_simp, self.num_views, ft_dim=self.num_features,
                                              cameras=cameras, fts=fts, use_lr_features=self.use_lr_features, pix2face=pix2face, route=route, **size)
         verts = self._verts(mesh_simp)
-        net_route = "torch" if route == "host" else route
+        net_route = _routes.torch_route(route)
         if isinstance(operators, PackedOperators):
             if len(operators.n_verts) != 1:
                 raise ValueError("forward takes one mesh: a PackedOperators of several meshes goes to forward_many")

@@ -24,7 +24,8 @@ Routes:
 import numpy as np
 import torch
 
-from ._operands import lift_cameras, lift_mesh, lift_pix2face
+from . import _routes
+from ._operands import image_frame, lift_cameras, lift_mesh, lift_pix2face
 
 # where tools/lift_time.py measured the device route (its own raster pass included) not slower than the torch route on an MI355X
 # (README.md), by the layout of the maps: 1.07 ms against 32.5 ms (NCHW), 0.38 ms against 17.4 ms (channels-last)
@@ -41,14 +42,6 @@ def mesh_arrays(mesh):
     if isinstance(mesh, (tuple, list)) and len(mesh) == 2:
         return mesh[0], mesh[1]
     raise TypeError("a mesh is an object with verts_list() / faces_list() or a (verts, faces) pair")
-
-
-def _check_square(H, W, who):
-    if int(H) != int(W):
-        raise ValueError(f"{who}: square images only (H = {H}, W = {W})")
-    if int(H) <= 0:
-        raise ValueError(f"{who}: H and W must be positive")
-    return int(H), int(W)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -112,34 +105,15 @@ def _torch_lift(maps, verts, faces, R, T, pix2face, focal_length, device):
     return torch.where(seen_by[:, None] > 0, total / seen_by.clamp(min=1)[:, None], total), seen_by
 
 
-def _engine():
-    if not torch.cuda.is_available():
-        return None
-    from .engine import default_engine
-    return default_engine()
-
-
 def _layout(ft):
     return "channels_last" if ft.dim() == 4 and ft.stride(1) == 1 and ft.shape[1] > 1 else "nchw"
-
-
-def _pick(route, fts_list):
-    if route not in ("auto", "host", "device"):
-        raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
-    if route == "device":
-        if _engine() is None:
-            raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-        return "device"
-    if route == "auto" and _engine() is not None and all(AUTO_DEVICE[_layout(ft)] for ft in fts_list):
-        return "device"
-    return route
 
 
 def _as_maps(fts, who):
     ft = fts if isinstance(fts, torch.Tensor) else torch.as_tensor(np.asarray(fts))
     if ft.dim() != 4:
         raise ValueError(f"{who}: fts must be (views, C, H, W): one feature map per camera")
-    _check_square(ft.shape[2], ft.shape[3], who)
+    image_frame(ft.shape[2], ft.shape[3], None, who)
     return ft
 
 
@@ -154,9 +128,9 @@ def lift_features_many(fts_list, meshes, cameras_list, pix2face_list=None, route
         raise ValueError(f"{who}: one stack of maps, one mesh and one (R, T) pair per mesh")
     pairs = [mesh_arrays(m) for m in meshes]
     maps = [_as_maps(ft, f"{who}: mesh {b}") for b, ft in enumerate(fts_list)]
-    picked = _pick(route, maps)
+    picked = _routes.pick_host(route, all(AUTO_DEVICE[_layout(ft)] for ft in maps))      # "auto" left: torch where the maps lie
     if picked == "device":
-        out = _engine().lift_features(maps, [p[0] for p in pairs], [p[1] for p in pairs], cameras_list, pix2face_list=pix2face_list,
+        out = _routes.engine_or_none().lift_features(maps, [p[0] for p in pairs], [p[1] for p in pairs], cameras_list, pix2face_list=pix2face_list,
                                       return_counts=return_counts, focal_length=focal_length)
         feats, cnts = out if return_counts else (out, None)
     else:
@@ -186,16 +160,11 @@ def rasterize_visibility(mesh_simp, cameras, H, W, route="auto", focal_length=1.
     pixel, kept where they project strictly inside the frame).  route 'host': float64 NumPy; 'device': dm_raster_pix2face; 'auto': the
     device when a GPU is present."""
     who = "rasterize_visibility"
-    H, W = _check_square(H, W, who)
+    H, W = image_frame(H, W, None, who)
     V, F = lift_mesh(*mesh_arrays(mesh_simp), who)
     R, T = lift_cameras(cameras, who)
-    if route not in ("auto", "host", "device"):
-        raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
-    eng = None if route == "host" else _engine()
-    if route == "device" and eng is None:
-        raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-    if eng is not None:
-        p2f, vis = eng.raster_visibility([V], [F], [(R, T)], H, W, focal_length)
+    if _routes.pick_host(route) == "device":
+        p2f, vis = _routes.engine_or_none().raster_visibility([V], [F], [(R, T)], H, W, focal_length)
         return p2f[0], vis[0]
     p2f = np.stack([host_raster(V, F, R[v], T[v], H, W, focal_length) for v in range(R.shape[0])])
     vis = np.zeros((R.shape[0], V.shape[0]), bool)
@@ -232,5 +201,5 @@ def get_features_per_vertex(device, extractor, mesh, mesh_simp, num_views, ft_di
         cameras = (camera.R, camera.T)
         maps = [extractor(renders[idx][..., :3])[1 if use_lr_features else 0] for idx in range(len(renders))]
         fts = torch.cat([ft if ft.dim() == 4 else ft[None] for ft in maps])
-    _check_square(H, W, who)
+    image_frame(H, W, None, who)
     return lift_features_many([fts], [mesh_simp], [cameras], None if pix2face is None else [pix2face], route=route, device=device)[0]

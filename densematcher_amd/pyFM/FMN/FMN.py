@@ -6,7 +6,7 @@ Functional map networks: consistent latent bases and Consistent ZoomOut, with th
     net.zoomout_refine(nit=10, step=2, subsample=500, weight_type='icsm')
     net.maps[(i, j)], net.p2p[(i, j)], net.CCLB
 
-Routing (the pattern of densematcher_amd.utils._engine): `device=None` takes the device when the process has a GPU and DEVICE_DEFAULT is
+Routing (densematcher_amd._routes.engine_for): `device=None` takes the device when the process has a GPU and DEVICE_DEFAULT is
 set, `device=True` / `device=False` force a route (True without a GPU fails as MatchEngine() does: there is no silent fall-back).
 
 Host route: the reference's computation in NumPy / SciPy -- the restatement the tests pin to the recorded reference -- with three
@@ -37,21 +37,12 @@ import numpy as np
 import scipy.linalg
 import scipy.sparse as sparse
 
+from ... import _routes
+
 # Whether device=None means the device in a process with a GPU.  Set from the measurement in DESIGN.md ("Functional map networks").
 DEVICE_DEFAULT = True
 
 MAX_DIM, MAX_M = 4096, 256          # limits of the device route: n M and M (MatchEngine.FMN_MAX_DIM / FMN_MAX_M)
-
-
-def _engine(device):
-    """the engine of the device route, or None for the host route"""
-    if device is None:
-        import torch
-        device = DEVICE_DEFAULT and torch.cuda.is_available()
-    if not device:
-        return None
-    from ...engine import default_engine
-    return default_engine()
 
 
 def _is_tensor(x):
@@ -148,7 +139,7 @@ class FMN:
 
     def __init__(self, meshlist, maps_dict=None, device=None):
         self.meshlist = copy.deepcopy(meshlist)
-        self._eng = _engine(device)
+        self._eng = _routes.engine_for(device, DEVICE_DEFAULT)
 
         self.edges = None           # sorted list of (i, j)
         self._maps = None           # host route: dict; device route: (E, L, L) tensor in the order of `edges`

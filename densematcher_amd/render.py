@@ -36,9 +36,10 @@ Loading OBJ / MTL / image files is outside this package.
 import numpy as np
 import torch
 
+from . import _routes
 from ._engine_render import AMBIENT, BACKGROUND, DIFFUSE, SHININESS, SPECULAR, shade_params
-from ._operands import lift_cameras, lift_mesh, render_normals, render_points, render_texture
-from .projection import _check_square, _engine, host_raster, mesh_arrays
+from ._operands import image_frame, lift_cameras, lift_mesh, render_normals, render_points, render_texture
+from .projection import host_raster, mesh_arrays
 
 # whether route="auto" takes the device in a process with a GPU: where tools/render_time.py measured the device route not slower than the
 # host route on an MI355X (README.md): 4.4 ms against 9.9 s for one mesh of 102 400 faces, five 512 x 512 views
@@ -189,16 +190,6 @@ def _host_view(V, F, R, T, H, W, focal, tex, normals, light, shade):
 
 
 # ------------------------------------------------------------------------------------------------------------------ public
-def _pick(route):
-    if route not in ("auto", "host", "device"):
-        raise ValueError(f"route must be 'auto', 'host' or 'device', not {route!r}")
-    if route == "device":
-        if _engine() is None:
-            raise RuntimeError("route='device' needs a ROCm GPU (gfx950)")
-        return "device"
-    return "device" if route == "auto" and AUTO_DEVICE and _engine() is not None else "host"
-
-
 def default_cameras(verts, num_views, center, device="cpu", add_angle_azi=0, add_angle_ele=0):
     """((R, T), center) as run_rendering places them without cameras (render.py:21-26): radius = max |bounding box|, centre = the
     bounding box's mean unless given, get_uniform_SO3_RT at distance 2 radius"""
@@ -222,7 +213,7 @@ def render_many(device, meshes, num_views, H, W, cameras_list=None, centers=None
     torch.float32 | torch.float16 a sixth entry, the RGB planes (views, 3, H, W)."""
     who = "render_many"
     Bn = len(meshes)
-    H, W = _check_square(H, W, who)
+    H, W = image_frame(H, W, None, who)
     cameras_list = [None] * Bn if cameras_list is None else list(cameras_list)
     centers = [None] * Bn if centers is None else list(centers)
     if Bn == 0 or len(cameras_list) != Bn or len(centers) != Bn or (light_location is not None and len(light_location) != Bn):
@@ -236,9 +227,8 @@ def render_many(device, meshes, num_views, H, W, cameras_list=None, centers=None
             cam = cameras_list[b]
         cams.append(cam)
     textures = [texture_of(m) for m in meshes]
-    picked = _pick(route)
-    if picked == "device":
-        out = _engine().render_phong([p[0] for p in pairs], [p[1] for p in pairs], cams, H, W, textures, normals_list, light_location,
+    if _routes.pick_host(route, AUTO_DEVICE) == "device":
+        out = _routes.engine_or_none().render_phong([p[0] for p in pairs], [p[1] for p in pairs], cams, H, W, textures, normals_list, light_location,
                                      ambient_color, diffuse_color, specular_color, shininess, background_color, focal_length, planes)
         images, zbufs, p2fs, pls = out.images, out.zbuf, out.pix2face, out.planes
     else:

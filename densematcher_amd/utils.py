@@ -9,7 +9,7 @@ D[np.ix_(g_i, g_j)] with SciPy and takes the mean matched distance.  On the devi
 (MatchEngine.groups_dmtx -> dm_lsa_gather): the same assignments, ties included; the means agree with the reference's to the
 rounding of a sum of min(|g_i|, |g_j|) terms (NumPy adds them pairwise, the kernel in row order).
 
-Routing (the pattern of pyFM.mesh.geometry.graph_engine): `device=None` takes the device when the process has a GPU and
+Routing (_routes.engine_for): `device=None` takes the device when the process has a GPU and
 DEVICE_DEFAULT is set, else the reference's SciPy loop on the host; `device=True` / `device=False` force a route
 (device=True without a GPU fails as MatchEngine() does: there is no silent fall-back).
 """
@@ -17,21 +17,12 @@ import os
 
 import numpy as np
 
+from . import _routes
+
 # Whether device=None means the device in a process with a GPU.  Set from the measurement in DESIGN.md ("Semantic group
 # distances"): the device route is the default only because its single-mesh time was below the host loop's at every
 # group count measured.
 DEVICE_DEFAULT = True
-
-
-def _engine(device):
-    """the engine of the device route, or None for the host route"""
-    if device is None:
-        import torch
-        device = DEVICE_DEFAULT and torch.cuda.is_available()
-    if not device:
-        return None
-    from .engine import default_engine
-    return default_engine()
 
 
 def _host_pair(D, group1, group2):
@@ -53,7 +44,7 @@ def get_distance_between_groups(geodesic_distmat, group1, group2, device=None):
     the environment)."""
     if len(group1) == 0 or len(group2) == 0:
         return _empty_pair()
-    eng = _engine(device)
+    eng = _routes.engine_for(device, DEVICE_DEFAULT)
     if eng is None:
         return _host_pair(np.asarray(geodesic_distmat), group1, group2)
     return eng.lsa_gather(geodesic_distmat, [group1], [group2])[0]
@@ -87,7 +78,7 @@ def get_groups_dmtx(geodesic_distmat, groups, device=None):
     not, Dijkstra's not in the last bit), so the orientation is part of the result -- and [j, i] is a copy of it.
     The reference marks entries that are not computed yet with -1 and therefore computes [j, i] afresh when a mean is
     exactly -1; that cannot happen for distances and is NOT mirrored: [j, i] is always the copy."""
-    eng = _engine(device)
+    eng = _routes.engine_for(device, DEVICE_DEFAULT)
     if eng is None:
         return _host_dmtx(geodesic_distmat, groups)
     _warn_empty(groups)
@@ -103,7 +94,7 @@ def get_groups_dmtx_many(geodesic_distmats, groups_list, device=None):
     """get_groups_dmtx for several meshes: a list of (n_b, n_b) matrices (any sizes) or one padded (B, N, N) array / device
     tensor, and one list of groups per mesh.  ONE device call for the batch.  Returns a list of (G_b, G_b) arrays."""
     groups_list = [list(g) for g in groups_list]
-    eng = _engine(device)
+    eng = _routes.engine_for(device, DEVICE_DEFAULT)
     stacked = _is_tensor(geodesic_distmats) or (isinstance(geodesic_distmats, np.ndarray) and geodesic_distmats.ndim == 3)
     if len(geodesic_distmats) != len(groups_list):
         raise ValueError(f"get_groups_dmtx_many: {len(groups_list)} lists of groups for {len(geodesic_distmats)} matrices")
