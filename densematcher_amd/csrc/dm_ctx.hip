@@ -54,7 +54,6 @@ extern "C" int dm_destroy(dm_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     for (hipEvent_t e : ctx->prof_events) (void)hipEventDestroy(e);
     if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->gram_keep) (void)hipFree(ctx->gram_keep);
     for (auto& e : ctx->stats) { if (e.buf[0]) (void)hipFree(e.buf[0]); }
     if (ctx->pinned_words) (void)hipHostFree(ctx->pinned_words);
     if (ctx->pinned_event) (void)hipEventDestroy(ctx->pinned_event);
@@ -101,7 +100,6 @@ extern "C" int dm_set_option(dm_ctx* ctx, const char* name, int value) {
     else if (n == "graph_geod_device") ctx->opt_graph_geod_device = value;
     else if (n == "fmn_eig_route") ctx->opt_fmn_eig_route = value;
     else if (n == "proj_onepass") ctx->opt_proj_onepass = value;
-    else if (n == "energy_keep_gram") { ctx->opt_energy_keep_gram = value; ctx->gram_valid = false; }
     else return dm_fail(ctx, DM_EINVAL, "dm_set_option: unknown option '%s'", name);
     return DM_OK;
 }

@@ -165,7 +165,7 @@ __global__ __launch_bounds__(256) void m_finish_stats_kernel(const double* __res
 //   rs_i = E2_i . p,  p = sum_j a1_j Phi1_j (k1)        cs_j = a1_j Phi1_j . q,  q = sum_i E2_i = C^T s2,  s2 = sum_i Phi2_i (k2)
 // -- O(N k) instead of a pass over the N2 x N1 tiles.  When only w_sumto1 asks for statistics (the notebook's terms; the sums
 // of squares of w_stochastic still take the tile pass) two small kernels replace em_stats_kernel + m_finish_stats_kernel:
-//   em_basis_sums_kernel    p and s2: they do not depend on C (kept across an optimiser's evaluations, option "energy_keep_gram")
+//   em_basis_sums_kernel    p and s2: they do not depend on C (kept across a fit's evaluations in the keep block of dm_fmap_fit_steps)
 //   em_stats_linear_kernel  a workgroup per 256 rows: q from s2 and C, then rs, cs and the block's shares of their totals
 // (fixed summation orders; rsq / csq are zeroed: their terms carry a zero weight).  A single workgroup per pair doing all
 // of it took 32 us -- nothing hides its loads -- against 22 + 12 us for the tile pass; this form takes 7.
@@ -655,10 +655,17 @@ __global__ __launch_bounds__(256) void combine_kernel(double* __restrict__ grad,
     if (t == 0) energy[b] = (qa.C ? eq : e_quad[b]) + (cm.pe ? e_m : 0.0) + (e_dc ? w_dc * e_dc[b] : 0.0) + (es ? es[b] : 0.0);
 }
 
-extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1,
-                                   const float* Phi2, int ld2, const float* mass1, const float* A, const float* Bm,
-                                   const double* lam1, const double* lam2, const double* ops1, const double* ops2, int n_ops,
-                                   const double* weights, const double* C, double* energy, double* grad) {
+// What an evaluation computes that does not depend on C, as one block a fit's caller owns: P = A A^T and Q = Bm A^T stacked,
+// (B, k1 + k2, k1), then the basis sums p (B, k1) and s2 (B, k2) of em_basis_sums_kernel
+extern "C" size_t dm_fmap_fit_keep_bytes(int B, int k1, int k2) {
+    return ((size_t)B * (k1 + k2) * k1 + (size_t)B * (k1 + k2)) * 8;
+}
+
+// dm_fmap_energy_grad with that block (null: none), written by this evaluation or, keep_valid, read from an earlier one of the fit
+int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1, const float* Phi2,
+                             int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1, const double* lam2,
+                             const double* ops1, const double* ops2, int n_ops, const double* weights, const double* C, double* energy,
+                             double* grad, double* keep, bool keep_valid) {
     if (!ctx) return DM_EINVAL;
     DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && k1 > 0 && k2 > 0 && D > 0, "sizes must be positive");
     DM_REQUIRE(ctx, A && Bm && lam1 && lam2 && weights && C && energy && grad, "null pointer");
@@ -707,32 +714,8 @@ extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, i
     if (shape) need += dm_align_up((size_t)B * 2 * k1 * k1 * 8) + dm_align_up(bKK) + dm_align_up((size_t)B * 8) + 4096;
     int rc = dm_ws_reserve(ctx, need);
     if (rc) return rc;
-    double* PQ = (double*)dm_ws_take(ctx, (size_t)B * (k1 + k2) * k1 * 8);
-    // P, Q do not depend on C: an L-BFGS driver asks to keep them across its evaluations (option "energy_keep_gram")
-    const bool keep_gram = ctx->opt_energy_keep_gram != 0;
-    bool sums_valid = false;                               // (p, s2 of the indicator statistics ride along with P, Q)
-    if (keep_gram) {
-        const size_t gb = (size_t)B * (k1 + k2) * k1 * 8 + (size_t)B * (k1 + k2) * 8;      // P, Q | p, s2 (em_basis_sums_kernel)
-        const bool same = ctx->gram_valid && ctx->gram_key_ptr[2] == (const void*)Phi1 && ctx->gram_key_ptr[3] == (const void*)Phi2 &&
-                          ctx->gram_key_ptr[4] == (const void*)mass1 && ctx->gram_key_dim[4] == N1 && ctx->gram_key_dim[5] == N2 && ctx->gram_key_ptr[0] == (const void*)A && ctx->gram_key_ptr[1] == (const void*)Bm &&
-                          ctx->gram_key_dim[0] == B && ctx->gram_key_dim[1] == k1 && ctx->gram_key_dim[2] == k2 && ctx->gram_key_dim[3] == D;
-        if (!same) {
-            ctx->gram_valid = false;
-            if (gb > ctx->gram_keep_bytes) {
-                DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->gram_keep) DM_CHECK_HIP(ctx, hipFree(ctx->gram_keep));
-                ctx->gram_keep = nullptr; ctx->gram_keep_bytes = 0;
-                DM_CHECK_HIP(ctx, hipMalloc((void**)&ctx->gram_keep, gb));
-                ctx->gram_keep_bytes = gb;
-            }
-            ctx->gram_key_ptr[0] = A; ctx->gram_key_ptr[1] = Bm; ctx->gram_key_ptr[2] = Phi1; ctx->gram_key_ptr[3] = Phi2; ctx->gram_key_ptr[4] = mass1;
-            ctx->gram_key_dim[4] = N1; ctx->gram_key_dim[5] = N2;
-            ctx->gram_key_dim[0] = B; ctx->gram_key_dim[1] = k1; ctx->gram_key_dim[2] = k2; ctx->gram_key_dim[3] = D;
-        }
-        PQ = ctx->gram_keep;
-        sums_valid = ctx->gram_valid && ctx->gram_sums_valid;
-        if (!ctx->gram_valid) ctx->gram_sums_valid = false;
-    }
+    double* PQ = keep ? keep : (double*)dm_ws_take(ctx, (size_t)B * (k1 + k2) * k1 * 8);
+    const bool reuse = keep && keep_valid;                 // P, Q (and p, s2 behind them) are what an earlier evaluation of the fit wrote
     double* CP = (double*)dm_ws_take(ctx, bKK);
     double* Gm = (double*)dm_ws_take(ctx, bKK);
     double* G1 = (double*)dm_ws_take(ctx, bKK);
@@ -748,10 +731,9 @@ extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, i
         KRowsStackedF32 opa{A, Bm, k1, k2, D};
         KRowsF32 opb{A, (long long)k1 * D, D, k1, D};
         OutNT out{PQ, (long long)(k1 + k2) * k1, k1};
-        if (!keep_gram || !ctx->gram_valid)
+        if (!reuse)
             DM_LAUNCH(ctx, "energy_gram_nt_f64", (gemm_nt_f64<KRowsStackedF32, KRowsF32, OutNT>),
                       dim3(dm_cdiv(k1 + k2, NT_T) * dm_cdiv(k1, NT_T), 1, B), dim3(256), 0, opa, opb, out, k1 + k2, k1, D);
-        if (keep_gram) ctx->gram_valid = true;
         KRowsF64 ca{C, (long long)k2 * k1, k1, k2, k1, 0};
         KRowsF64 pb{PQ, (long long)(k1 + k2) * k1, k1, k1, k1, 1};          // (C P)_ij = sum_k C_ik P_kj
         OutNT ocp{CP, (long long)k2 * k1, k1};
@@ -803,14 +785,13 @@ extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, i
         ep.rs = rs; ep.rsq = rsq; ep.pcs = pcs; ep.pcsq = pcsq; ep.ngroups = ngroups; ep.cs = cs; ep.csq = csq; ep.stat = stat; ep.nstat = nstat;
         ep.w = mw; ep.Y = Yv; ep.pe = pe;
         if (stats && !(mw.stoch > 0) && k2 <= 256) {
-            double* pv = keep_gram ? ctx->gram_keep + (size_t)B * (k1 + k2) * k1 : (double*)dm_ws_take(ctx, (size_t)B * k1 * 8);
-            double* s2 = keep_gram ? pv + (size_t)B * k1 : (double*)dm_ws_take(ctx, (size_t)B * k2 * 8);
+            double* pv = keep ? keep + (size_t)B * (k1 + k2) * k1 : (double*)dm_ws_take(ctx, (size_t)B * k1 * 8);
+            double* s2 = keep ? pv + (size_t)B * k1 : (double*)dm_ws_take(ctx, (size_t)B * k2 * 8);
             if (!pv || !s2) return dm_fail(ctx, DM_ENOMEM, "energy: workspace not reserved");
-            if (!keep_gram || !sums_valid) {
+            if (!reuse) {
                 int cw = 16;
                 while (cw < k1 || cw < k2) cw <<= 1;           // (k1 <= 256; a wider k2 takes the tile pass below)
                 DM_LAUNCH(ctx, "energy_basis_sums", em_basis_sums_kernel, dim3(B), dim3(1024), 0, Phi1, ld1, mass1, N1, k1, Phi2, ld2, N2, k2, cw, pv, s2);
-                if (keep_gram) ctx->gram_sums_valid = true;
             }
             DM_LAUNCH(ctx, "energy_stats_linear", em_stats_linear_kernel, dim3(nstat, B), dim3(256), 0, E2, Phi1, ld1, mass1, N1, N2, k1, k2,
                       C, (const double*)pv, (const double*)s2, rs, rsq, cs, csq, stat, e2_inline ? Phi2 : (const float*)nullptr, ld2);
@@ -901,7 +882,15 @@ extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, i
     return DM_OK;
 }
 
-// ops[b][d] = Phi^T diag(mass * F[:, d]) Phi   (k x k float64) for every descriptor d
+extern "C" int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1,
+                                   const float* Phi2, int ld2, const float* mass1, const float* A, const float* Bm,
+                                   const double* lam1, const double* lam2, const double* ops1, const double* ops2, int n_ops,
+                                   const double* weights, const double* C, double* energy, double* grad) {
+    return dm_fmap_energy_grad_keep(ctx, B, N1, N2, k1, k2, D, Phi1, ld1, Phi2, ld2, mass1, A, Bm, lam1, lam2, ops1, ops2, n_ops, weights, C,
+                               energy, grad, nullptr, false);
+}
+
+// ops[b][d] = Phi^T diag(mass * F[:, d]) Phi  (k x k float64) for every descriptor d
 extern "C" int dm_fmap_descr_ops(dm_ctx* ctx, int B, int N, int D, int k, const float* Phi, int ld, const float* mass, const void* F,
                                  int f_dtype, double* ops) {
     if (!ctx) return DM_EINVAL;

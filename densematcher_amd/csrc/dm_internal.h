@@ -15,8 +15,9 @@
 
 // (abi N: bumped whenever an existing entry point changes what it reads or writes -- abi 5: dm_fmap_energy_grad / dm_fmap_fit_steps read TEN
 //  weights (w_area, w_conformal appended in round 4); dm_eigenbasis warm_start = 2; dm_laplacian_*, dm_fmap_fit_fused added; abi 6: dm_fmap_fit_fused takes the element loop's precision
-//  as the argument element_f32, the option "fit_f32" is gone)
-#define DM_VERSION_STRING "densematch 0.5.0 (gfx950, abi 6)"
+//  as the argument element_f32, the option "fit_f32" is gone; abi 7: dm_fmap_fit_steps takes keep, keep_valid, n_running after maxls
+//  (dm_fmap_fit_keep_bytes added), the option "energy_keep_gram" and the context's kept Gram block are gone)
+#define DM_VERSION_STRING "densematch 0.5.0 (gfx950, abi 7)"
 
 struct dm_ctx {
     int device = 0;
@@ -64,16 +65,7 @@ struct dm_ctx {
                                  // 1 = dm_fps_graph / dm_graph_geodesic, 0 = SciPy's Dijkstra on the host; the same bits; the library only keeps the value
     int opt_fmn_eig_route = 0;   // the Python layer's choice for the eigenproblem of a functional map network (MatchEngine.eigh_smallest): 0 by the sizes,
                                  // 1 the full Jacobi eigendecomposition, 2 the filtered iteration; the library only keeps the value
-    int opt_energy_keep_gram = 0;  // 1: dm_fmap_energy_grad keeps P = A A^T, Q = B A^T of its FIRST call and reuses them while A, B
-                                   // (pointers and sizes) stay the same: the caller promises not to change their contents (the L-BFGS
-                                   // driver: the projected descriptors are fixed during a fit).  Setting the option again drops them.
-    double* gram_keep = nullptr;   // (its own allocation: the workspace arena is recycled by every call)
-    size_t gram_keep_bytes = 0;
-    const void* gram_key_ptr[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int gram_key_dim[6] = {0, 0, 0, 0, 0, 0};
-    bool gram_valid = false;
-    bool gram_sums_valid = false;  // the basis sums p, s2 behind P, Q in the same block (written by the first evaluation that needs them)
-    int n_cu = 0;                // multiProcessorCount of the device
+    int n_cu = 0;               // multiProcessorCount of the device
     int32_t* pinned_words = nullptr;   // 64 ints of page-locked host memory + an event: small device -> host reads that must not stall the
     hipEvent_t pinned_event = nullptr; // launch queue (dm_pinned_words; the ICP's "have all polar iterations converged?")
     // Per-basis statistics kept between calls (dm_fm_to_p2p: the per-64-vertex maxima of |Phi2|, from which the power-of-two scale of
@@ -346,6 +338,13 @@ __device__ __forceinline__ void dm_c00_body(const dm_c00_args<TR>& z, int b, int
     }
 }
 #endif
+
+// dm_fmap_energy_grad's body (dm_energy.hip).  keep: a block of dm_fmap_fit_keep_bytes the caller owns, or null (P, Q and the basis
+// sums are recomputed in the arena); keep_valid: an earlier evaluation with the same operands and weights wrote it, else this one does
+int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1, const float* Phi2,
+                             int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1, const double* lam2,
+                             const double* ops1, const double* ops2, int n_ops, const double* weights, const double* C, double* energy,
+                             double* grad, double* keep, bool keep_valid);
 
 // eigendecomposition of B symmetric m x m matrices by the Jacobi kernel of dm_eigen.hip (H overwritten, V scratch (B, m, m)):
 // theta (B, m) ascending, Q (B, m, m) eigenvectors as columns

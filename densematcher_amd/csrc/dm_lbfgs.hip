@@ -78,20 +78,44 @@ extern "C" int dm_lbfgs_result(dm_ctx* ctx, int B, int n, int m, const void* sta
     return DM_OK;
 }
 
+// the number of pairs whose status is still LB_RUN (one workgroup: a plain integer sum)
+__global__ __launch_bounds__(256) void lbfgs_count_running_kernel(int B, const int* __restrict__ ic, int* __restrict__ nrun) {
+    __shared__ int sh[4];
+    int c = 0;
+    for (int b = threadIdx.x; b < B; b += 256) c += ic[(long long)b * LI_NINT + LI_STATUS] == LB_RUN;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) *nrun = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
 // nsteps x (energy + gradient at the trial points -> advance): the evaluation loop of a fit on the library side of the ABI
 extern "C" int dm_fmap_fit_steps(dm_ctx* ctx, int nsteps, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1,
                                  const float* Phi2, int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1,
                                  const double* lam2, const double* ops1, const double* ops2, int n_ops, const double* weights, int m,
                                  void* state, double* x_trial, double* energy, double* grad, double ftol, double pgtol, int maxiter,
-                                 int maxfun, int maxls) {
+                                 int maxfun, int maxls, double* keep, int keep_valid, int* n_running) {
     if (!ctx) return DM_EINVAL;
     DM_REQUIRE(ctx, nsteps > 0 && state && x_trial && energy && grad, "fit_steps: null pointer or no steps");
-    for (int s = 0; s < nsteps; ++s) {
-        int rc = dm_fmap_energy_grad(ctx, B, N1, N2, k1, k2, D, Phi1, ld1, Phi2, ld2, mass1, A, Bm, lam1, lam2, ops1, ops2, n_ops, weights,
-                                     x_trial, energy, grad);
+    for (int s = 0; s < nsteps; ++s) {      // (the evaluations after a call's first read what the first one left in `keep`)
+        int rc = dm_fmap_energy_grad_keep(ctx, B, N1, N2, k1, k2, D, Phi1, ld1, Phi2, ld2, mass1, A, Bm, lam1, lam2, ops1, ops2, n_ops, weights,
+                                          x_trial, energy, grad, keep, s > 0 || keep_valid != 0);
         if (rc) return rc;
         rc = dm_lbfgs_advance(ctx, B, k2 * k1, m, state, energy, grad, x_trial, ftol, pgtol, maxiter, maxfun, maxls);
         if (rc) return rc;
+    }
+    if (n_running) {                        // one word to the host, as dm_icp reads its counters: pinned memory and the context's event
+        lb_layout L = lb_carve(state, B, k2 * k1, m);
+        int32_t* host_words = nullptr;
+        hipEvent_t host_ev = nullptr;
+        int rc = dm_pinned_words(ctx, &host_words, &host_ev);
+        if (rc) return rc;
+        DM_LAUNCH(ctx, "lbfgs_count_running", lbfgs_count_running_kernel, dim3(1), dim3(256), 0, B, L.ic, L.nrun);
+        DM_CHECK_HIP(ctx, hipMemcpyAsync(host_words, L.nrun, 4, hipMemcpyDeviceToHost, ctx->stream));
+        DM_CHECK_HIP(ctx, hipEventRecord(host_ev, ctx->stream));
+        DM_CHECK_HIP(ctx, hipEventSynchronize(host_ev));
+        *n_running = host_words[0];
     }
     return DM_OK;
 }

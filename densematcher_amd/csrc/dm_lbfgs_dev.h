@@ -324,7 +324,7 @@ __device__ __forceinline__ void lb_advance_pair(const int b, int n, lbfgs_opts o
 }
 
 
-struct lb_layout { double *x, *g, *d, *S, *Y, *rho, *al, *sc; int* ic; };
+struct lb_layout { double *x, *g, *d, *S, *Y, *rho, *al, *sc; int* ic; int* nrun; };   // nrun: one word in the slack behind ic
 static inline size_t lb_state_bytes(int B, int n, int m) {
     return ((size_t)B * n * 3 + (size_t)B * m * n * 2 + (size_t)B * m * 2 + (size_t)B * LS_NSCAL) * 8 + (size_t)B * LI_NINT * 4 + 1024;
 }
@@ -340,5 +340,6 @@ static inline lb_layout lb_carve(void* state, int B, int n, int m) {
     L.al = p; p += (size_t)B * m;
     L.sc = p; p += (size_t)B * LS_NSCAL;
     L.ic = (int*)p;
+    L.nrun = L.ic + (size_t)B * LI_NINT;                  // pairs still LB_RUN after the last advance of dm_fmap_fit_steps
     return L;
 }

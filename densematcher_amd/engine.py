@@ -34,10 +34,6 @@ from ._engine_render import _RenderOps
 from ._operands import fits_abi, host_ptr, ptr as _ptr
 
 
-class _KeepAlive(tuple):
-    """an argument tuple that also holds the tensors its raw pointers refer to"""
-
-
 class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps, _JbuOps, _AggreOps, _EvalOps, _NetworkOps):
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
@@ -132,7 +128,7 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
     def synchronize(self):
         self.stream.synchronize()
 
-    OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0, "energy_keep_gram": 0,
+    OPTION_DEFAULTS = {"simnn_pipe": 1, "simnn_persist": 1, "knn_split": 1, "p2p_split": 2, "solve_packed": 0, "solve_reg": 1, "simnn_band": 4, "lsa_reg": 2, "simnn_big": 0,
                        "p2pfm_direct": 1, "zoomout_fused": 1, "proj_onepass": 1, "fit_mfma": 1, "basis_stats": 1, "solve_pcg": 1,
                        "zoomout_sub_fused": 1, "fps_heat_route": 0, "graph_geod_device": 1, "fmn_eig_route": 0}
 
@@ -357,17 +353,18 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
     def energy_grad(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
         """Energy (B,) and gradient (B,k2,k1) of the functional-map objective for the weights in `weights` (dict with keys
         of WEIGHT_ORDER; reference energy_func_std / grad_energy_std, base_functions.py:480-763)."""
-        ev = self._energy_grad_args(Cm, A, Bm, lam1, lam2, weights, Phi1, Phi2, a1, ops1, ops2)
-        Cm = ev[-1]
-        B, k2, k1 = Cm.shape
-        energy = torch.empty((B,), dtype=torch.float64, device=self.device)
-        grad = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
-        self._chk(self.lib.dm_fmap_energy_grad(self.ctx, *ev[:-1], _ptr(Cm), _ptr(energy), _ptr(grad)))
+        o = self._fit_operands(Cm, A, Bm, lam1, lam2, weights, Phi1, Phi2, a1, ops1, ops2)
+        energy = torch.empty((o.B,), dtype=torch.float64, device=self.device)
+        grad = torch.empty((o.B, o.k2, o.k1), dtype=torch.float64, device=self.device)
+        self._chk(self.lib.dm_fmap_energy_grad(self.ctx, *o.head, *o.ops, o.w, _ptr(o.C), _ptr(energy), _ptr(grad)))
         return energy, grad
 
-    def _energy_grad_args(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
-        """the argument list dm_fmap_energy_grad and dm_fmap_fit_steps share (B ... weights), followed by the map tensor; the tensors
-        behind the pointers are kept alive by the tuple"""
+    def _fit_operands(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
+        """The operand list of a fit, once, for dm_fmap_energy_grad, dm_fmap_fit_steps and dm_fmap_fit_fused: the tensors on the device
+        (C the map or trial point, A, Bm, lam1, lam2, Phi1, Phi2, a1, ops1, ops2), the sizes (B, N1, N2, k1, k2, D, ld1, ld2, n_ops), the
+        ten weights as the host array `w`, and the two runs of arguments made of them: `head` (B ... lam2, what all three entry points
+        start with) and `ops` (ops1, ops2, n_ops).  The caller keeps the result in a local name until its library call has returned:
+        the pointers in `head` and `ops` refer to the tensors it holds."""
         Cm = self._dev(Cm, torch.float64, "C")
         A = self._dev(A, torch.float32, "A")
         Bm = self._dev(Bm, torch.float32, "Bm")
@@ -395,11 +392,11 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
             n_ops = ops1.shape[1]
             if ops1.shape != (B, n_ops, k1, k1) or ops2.shape != (B, n_ops, k2, k2):
                 raise ValueError("energy_grad: descriptor operators must be (B,D,k1,k1) and (B,D,k2,k2)")
-        keep = (Phi1, Phi2, a1, A, Bm, lam1, lam2, ops1, ops2, w)
-        args = _KeepAlive((B, N1, N2, k1, k2, D, _ptr(Phi1), ld1, _ptr(Phi2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1), _ptr(lam2),
-                           _ptr(ops1), _ptr(ops2), n_ops, C.cast(w, C.c_void_p), Cm))
-        args.keep = keep
-        return args
+        return types.SimpleNamespace(
+            C=Cm, A=A, Bm=Bm, lam1=lam1, lam2=lam2, Phi1=Phi1, Phi2=Phi2, a1=a1, ops1=ops1, ops2=ops2, w=C.cast(w, C.c_void_p),
+            B=B, N1=N1, N2=N2, k1=k1, k2=k2, D=D, ld1=ld1, ld2=ld2, n_ops=n_ops,
+            head=(B, N1, N2, k1, k2, D, _ptr(Phi1), ld1, _ptr(Phi2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1), _ptr(lam2)),
+            ops=(_ptr(ops1), _ptr(ops2), n_ops))
 
     # SciPy's L-BFGS-B defaults, i.e. what the reference's `minimize(..., options={'maxiter': maxiter})` runs with (functional.py:477)
     LBFGS_REFERENCE = {"maxcor": 10, "ftol": 2.220446049250313e-09, "gtol": 1e-5, "maxfun": 15000, "maxls": 20}
@@ -477,18 +474,13 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
         if precision not in ("auto", "f32", "f64"):
             raise ValueError("precision must be 'auto', 'f32' or 'f64'")
         f32 = precision == "f32" or (precision == "auto" and float(opts["ftol"]) >= 1e-10)
-        B, k1, D = A.shape
-        k2 = Bm.shape[1]
-        _, N1, ld1 = P1.shape
-        _, N2, ld2 = P2.shape
-        w = self._weight_array(dict(weights, w_dcomm=0.0))      # (reached only without operator lists: the commutativity term is off)
-        x0d = self._dev(x0, torch.float64, "x0")
-        xo = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
-        fo = torch.empty((B,), dtype=torch.float64, device=self.device)
-        info = torch.empty((B, 4), dtype=torch.int32, device=self.device)
+        # (reached only without operator lists: the commutativity term is off)
+        o = self._fit_operands(x0, A, Bm, lam1, lam2, dict(weights, w_dcomm=0.0), P1, P2, a1)
+        xo = torch.empty((o.B, o.k2, o.k1), dtype=torch.float64, device=self.device)
+        fo = torch.empty((o.B,), dtype=torch.float64, device=self.device)
+        info = torch.empty((o.B, 4), dtype=torch.int32, device=self.device)
         nev = C.c_int(0)
-        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
-                                             _ptr(lam2), C.cast(w, C.c_void_p), int(opts["maxcor"]), _ptr(x0d), float(opts["ftol"]), float(opts["gtol"]),
+        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, *o.head, o.w, int(opts["maxcor"]), _ptr(o.C), float(opts["ftol"]), float(opts["gtol"]),
                                              int(maxiter), int(opts["maxfun"]), int(opts["maxls"]), 1 if f32 else 0, _ptr(xo), _ptr(fo), _ptr(info),
                                              C.c_void_p(0), C.byref(nev)))
         return self._lbfgs_result(xo, fo, info, evaluations=int(nev.value), path="fused", element_loop="f32" if f32 else "f64")
@@ -506,25 +498,12 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
     def energy_grad_fused(self, Cm, A, Bm, lam1, lam2, weights, Phi1, Phi2, a1, precision="f64"):
         """energy (B,) and gradient (B,k2,k1) at the maps Cm through the arithmetic of dm_fmap_fit_fused (its single-evaluation mode):
         what the fused fit minimises, for tests and diagnostics.  precision "f64" | "f32": the element loop's (see _fit_fused)"""
-        Cm = self._dev(Cm, torch.float64, "C")
-        A = self._dev(A, torch.float32, "A")
-        Bm = self._dev(Bm, torch.float32, "Bm")
-        lam1 = self._dev(lam1, torch.float64, "lam1")
-        lam2 = self._dev(lam2, torch.float64, "lam2")
-        P1 = self._dev(Phi1, torch.float32, "Phi1")
-        P2 = self._dev(Phi2, torch.float32, "Phi2")
-        a1 = self._dev(a1, torch.float32, "a1")
-        B, k2, k1 = Cm.shape
-        D = A.shape[2]
-        _, N1, ld1 = P1.shape
-        _, N2, ld2 = P2.shape
-        w = self._weight_array(dict(weights, w_dcomm=0.0))
-        energy = torch.empty((B,), dtype=torch.float64, device=self.device)
-        grad = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
+        o = self._fit_operands(Cm, A, Bm, lam1, lam2, dict(weights, w_dcomm=0.0), Phi1, Phi2, a1)
+        energy = torch.empty((o.B,), dtype=torch.float64, device=self.device)
+        grad = torch.empty((o.B, o.k2, o.k1), dtype=torch.float64, device=self.device)
         if precision not in ("f32", "f64"):
             raise ValueError("precision must be 'f32' or 'f64'")
-        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, B, N1, N2, k1, k2, D, _ptr(P1), ld1, _ptr(P2), ld2, _ptr(a1), _ptr(A), _ptr(Bm), _ptr(lam1),
-                                             _ptr(lam2), C.cast(w, C.c_void_p), 0, _ptr(Cm), 0.0, 0.0, 0, 0, 0, 1 if precision == "f32" else 0,
+        self._chk(self.lib.dm_fmap_fit_fused(self.ctx, *o.head, o.w, 0, _ptr(o.C), 0.0, 0.0, 0, 0, 0, 1 if precision == "f32" else 0,
                                              C.c_void_p(0), _ptr(energy), C.c_void_p(0), _ptr(grad), None))
         return energy, grad
 
@@ -568,27 +547,23 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
         xt = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
         x0d = self._dev(x0, torch.float64, "x0")
         self._chk(self.lib.dm_lbfgs_init(self.ctx, B, n, m, _ptr(x0d), _ptr(state), _ptr(xt)))
-        # the per-pair integer state (status first) sits behind the float64 blocks of the state buffer
-        n_f64 = 3 * B * n + 2 * B * m * n + 2 * B * m + 16 * B
-        ints = state[n_f64:n_f64 + (8 * B * 4 + 7) // 8].view(torch.int32)[:8 * B].view(B, 8)
         nev, maxfun = 0, int(opts["maxfun"])
-        # the projected descriptors A, Bm are fixed during the fit: their Gram blocks are computed by the first evaluation only
-        keep_gram = self.get_option("energy_keep_gram")
-        self.set_option("energy_keep_gram", 1)
         # the evaluation loop itself runs behind the ABI, `check_every` evaluations per call (dm_fmap_fit_steps): a Python round per
         # evaluation cost more host time than the evaluation takes on the device for one small pair
-        ev = self._energy_grad_args(xt, A, Bm, lam1, lam2, weights, P1, P2, a1, ops1, ops2)
+        o = self._fit_operands(xt, A, Bm, lam1, lam2, weights, P1, P2, a1, ops1, ops2)
         energy = torch.empty((B,), dtype=torch.float64, device=self.device)
         grad = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
-        try:
-            while True:
-                self._chk(self.lib.dm_fmap_fit_steps(self.ctx, int(check_every), *ev[:-1], m, _ptr(state), _ptr(xt), _ptr(energy), _ptr(grad),
-                                                     float(opts["ftol"]), float(opts["gtol"]), int(maxiter), maxfun, int(opts["maxls"])))
-                nev += int(check_every)
-                if bool((ints[:, 0] != 0).all()) or nev > maxfun + 2:        # (one host synchronisation per check_every evaluations)
-                    break
-        finally:
-            self.set_option("energy_keep_gram", keep_gram)         # (the caller's setting; setting it drops what this fit kept)
+        # the projected descriptors and the bases are fixed during the fit: what an evaluation derives from them alone is written to
+        # this block by the fit's first evaluation and read by the others
+        keep = torch.empty(int(self.lib.dm_fmap_fit_keep_bytes(B, k1, k2)) // 8, dtype=torch.float64, device=self.device)
+        running = C.c_int(0)
+        while True:
+            self._chk(self.lib.dm_fmap_fit_steps(self.ctx, int(check_every), *o.head, *o.ops, o.w, m, _ptr(state), _ptr(xt), _ptr(energy), _ptr(grad),
+                                                 float(opts["ftol"]), float(opts["gtol"]), int(maxiter), maxfun, int(opts["maxls"]),
+                                                 _ptr(keep), 1 if nev else 0, C.byref(running)))
+            nev += int(check_every)
+            if running.value == 0 or nev > maxfun + 2:        # (one host synchronisation per check_every evaluations)
+                break
         xo = torch.empty((B, k2, k1), dtype=torch.float64, device=self.device)
         fo = torch.empty((B,), dtype=torch.float64, device=self.device)
         info = torch.empty((B, 4), dtype=torch.int32, device=self.device)

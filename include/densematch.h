@@ -78,9 +78,6 @@ size_t dm_workspace_bytes(const dm_ctx* ctx);
  *   "lsa_reg"       2 | 1 | 0   dm_linear_sum_assignment: column state in registers, started from a column reduction (kept per
  *                           matrix only when its optimum is provably unique, else redone) | the same in SciPy's order | LDS state
  *   "solve_reg"     1 | 0   dm_fmap_solve, k1 <= 129: register-resident solver (one wave per system) | the LDS-resident blocked one
- *   "energy_keep_gram" 0 | 1   dm_fmap_energy_grad: 1 = keep what does not depend on C (A A^T, B A^T, the mass-weighted column sums
- *                           of the bases) from the next call and reuse it while the same A, B, Phi1, Phi2, mass1 pointers and sizes are
- *                           passed; the caller promises not to change their CONTENTS meanwhile (an optimiser's evaluations of one fit).  Setting the option (to any value) drops what is kept.
  *   "zoomout_fused" 1 | 0   dm_zoomout on meshes of at least 256 vertices, maps up to 208: five launches per iteration (embedding + split
  *                           rows, biased-key search, merge, exact, p2p_to_FM) | six (seven with the reduce) through K-major copies
  *   "zoomout_sub_fused" 1 | 0   subsampled ZoomOut in the Python layer (refine.zoomout_refine(subsample=...), square map, one step size):
@@ -251,13 +248,23 @@ int dm_lbfgs_result(dm_ctx* ctx, int B, int n, int m, const void* state, double*
  * of one scipy.optimize.minimize call (pyFM/functional.py:477), nsteps evaluations at a time.  `energy` (B) and `grad` (B,k2,k1)
  * are scratch the caller owns; x_trial (B,k2,k1) is the trial point dm_lbfgs_init / the last advance left.  Pairs that have
  * stopped are not moved by further steps.  (A Python loop around the two calls costs more host time per evaluation than the
- * evaluation takes on the device for one small pair.) */
+ * evaluation takes on the device for one small pair.)
+ *   keep (nullable)     dm_fmap_fit_keep_bytes(B, k1, k2) bytes of device memory the caller owns, for what an evaluation computes
+ *                       that does not depend on the map: A A^T and Bm A^T stacked (B, k1 + k2, k1) fp64, then the mass-weighted
+ *                       column sums of the bases, p (B, k1) and s2 (B, k2).  NULL: every evaluation recomputes them in the workspace,
+ *                       as dm_fmap_energy_grad does.  The same bits either way.
+ *   keep_valid 0 | 1    0: the first evaluation of this call writes the block (the evaluations after it read it).  1: the block is
+ *                       read as it is; it must have been written by an earlier call of the same fit, with the same operands and weights.
+ *   n_running (host, nullable)   the number of pairs whose status is still 0 (running) after the call's last advance; asking for it
+ *                       is the call's one synchronisation with the device. */
+size_t dm_fmap_fit_keep_bytes(int B, int k1, int k2);
 int dm_fmap_fit_steps(dm_ctx* ctx, int nsteps, int B, int N1, int N2, int k1, int k2, int D,
                       const float* Phi1, int ld1, const float* Phi2, int ld2, const float* mass1,
                       const float* A, const float* Bm, const double* lam1, const double* lam2,
                       const double* ops1 /*nullable*/, const double* ops2 /*nullable*/, int n_ops,
                       const double* weights /*host, 10*/, int m, void* state, double* x_trial, double* energy, double* grad,
-                      double ftol, double pgtol, int maxiter, int maxfun, int maxls);
+                      double ftol, double pgtol, int maxiter, int maxfun, int maxls,
+                      double* keep /*nullable*/, int keep_valid, int* n_running /*host, nullable*/);
 
 /* The WHOLE iterative fit of small maps in one call: FunctionalMapping.fit (pyFM/functional.py:352-487) for maps up to 32 x 32 whose
  * energy has, besides w_descr / w_lap, only element-wise indicator terms and the sum-to-one term (w_p2p, w_ent, w_range01, w_sumto1:

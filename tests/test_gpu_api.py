@@ -809,12 +809,16 @@ def test_raw_non_delaunay_mesh_robust_laplacian():
           " p2p_21 agreement", float((maps[True][0] == maps[False][0]).mean()), " p2p_12 agreement", float((maps[True][1] == maps[False][1]).mean()))
 
 
-def test_energy_keep_gram_option():
-    """dm_set_option "energy_keep_gram": the Gram blocks of the projected descriptors are computed by the first evaluation and
-    reused while the same A, B are passed (the L-BFGS driver's case): identical energies and gradients with and without;
-    other operands, or setting the option again, recompute"""
+def test_fit_steps_keep_block():
+    """dm_fmap_fit_steps with a caller-owned keep block (dm_fmap_fit_keep_bytes): what an evaluation derives from the projected
+    descriptors and the bases alone is written by the evaluation that is told so (keep_valid = 0) and read by the others -- the same
+    trial points, energies, gradients and optimiser state, bit for bit, as with keep = NULL, one step per call or three; a fresh start
+    on the same block with other operands rewrites it; n_running is the number of status words still 0; the option that used to
+    carry the choice is gone and the driver touches no option"""
+    import ctypes as C
     import torch
-    from densematcher_amd.engine import default_engine
+    import lbfgs_restate as lr
+    from densematcher_amd.engine import default_engine, _ptr
     eng = default_engine()
     rng = np.random.default_rng(5)
     B, k1, k2, D = 2, 15, 17, 40
@@ -825,55 +829,101 @@ def test_energy_keep_gram_option():
     lam1, lam2 = np.sort(rng.uniform(0, 50, (B, k1)), axis=1), np.sort(rng.uniform(0, 50, (B, k2)), axis=1)
     w = {"w_descr": 1.0, "w_lap": 0.1}
     Cs = [rng.standard_normal((B, k2, k1)) for _ in range(3)]
-    plain = [eng.energy_grad(C, A, Bm, lam1, lam2, w) for C in Cs]
-    plain2 = eng.energy_grad(Cs[0], A2, Bm, lam1, lam2, w)
-    eng.set_option("energy_keep_gram", 1)
-    try:
-        kept = [eng.energy_grad(C, A, Bm, lam1, lam2, w) for C in Cs]
-        kept2 = eng.energy_grad(Cs[0], A2, Bm, lam1, lam2, w)            # other operand: recomputed
-        kept3 = eng.energy_grad(Cs[1], A, Bm, lam1, lam2, w)             # and back
-    finally:
-        eng.set_option("energy_keep_gram", 0)
-    for (e0, g0), (e1, g1) in zip(plain + [plain2, plain[1]], kept + [kept2, kept3]):
-        assert torch.equal(e0, e1) and torch.equal(g0, g1)
-    assert not torch.equal(plain2[0], plain[0][0])
-    # with the indicator statistics (w_sumto1: the bases' column sums ride along), other bases recompute
     N1, N2 = 300, 260
     e1 = torch.as_tensor((rng.standard_normal((B, N1, k1)) / np.sqrt(N1)).astype(np.float32)).to(dev)
     e2 = torch.as_tensor((rng.standard_normal((B, N2, k2)) / np.sqrt(N2)).astype(np.float32)).to(dev)
     e2b = torch.as_tensor((rng.standard_normal((B, N2, k2)) / np.sqrt(N2)).astype(np.float32)).to(dev)
     a1 = torch.as_tensor((rng.uniform(0.5, 1.5, (B, N1)) / N1).astype(np.float32)).to(dev)
     wm = {"w_descr": 1.0, "w_lap": 0.1, "w_sumto1": 2.0, "w_ent": 0.3}
-    calls = [(Cs[0], e2), (Cs[1], e2), (Cs[2], e2b), (Cs[0], e2)]
-    plain = [eng.energy_grad(C, A, Bm, lam1, lam2, wm, e1, p2, a1) for C, p2 in calls]
-    eng.set_option("energy_keep_gram", 1)
-    try:
-        kept = [eng.energy_grad(C, A, Bm, lam1, lam2, wm, e1, p2, a1) for C, p2 in calls]
-    finally:
-        eng.set_option("energy_keep_gram", 0)
-    for (e0, g0), (e1_, g1) in zip(plain, kept):
-        assert torch.equal(e0, e1_) and torch.equal(g0, g1)
-    for b in range(B):                                   # and the analytic sums against the oracle's dense indicator
+    l1d, l2d = torch.as_tensor(lam1).to(dev), torch.as_tensor(lam2).to(dev)
+    n, m = k2 * k1, 10
+    x0 = np.zeros((B, k2, k1))
+    x0[:, 0, 0] = 1.0
+    nbytes = int(eng.lib.dm_lbfgs_state_bytes(B, n, m))
+    assert int(eng.lib.dm_fmap_fit_keep_bytes(B, k1, k2)) == (B * (k1 + k2) * k1 + B * (k1 + k2)) * 8
+    keep = torch.empty(int(eng.lib.dm_fmap_fit_keep_bytes(B, k1, k2)) // 8, dtype=torch.float64, device=dev)
+    same = lambda a, b: torch.equal(a.view(torch.int64), b.view(torch.int64))          # (bits: a NaN would equal itself)
+
+    def fit(weights, A_, Bm_, P2, start, calls, keep_, maxfun=15000):
+        """one fit through the library, calls = [(nsteps, keep_valid), ...]: what every call left (trial points, energies, gradients, the
+        whole state block) and its n_running, which is checked against the status words of dm_lbfgs_result"""
+        wa = (C.c_double * 10)(*[float(weights.get(q, 0.0)) for q in eng.WEIGHT_ORDER])
+        state = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        xt, grad = torch.empty((2, B, k2, k1), dtype=torch.float64, device=dev)
+        energy = torch.empty((B,), dtype=torch.float64, device=dev)
+        xo, fo, info = torch.empty_like(xt), torch.empty_like(energy), torch.empty((B, 4), dtype=torch.int32, device=dev)
+        x0d = torch.as_tensor(start).to(dev)
+        eng._chk(eng.lib.dm_lbfgs_init(eng.ctx, B, n, m, _ptr(x0d), _ptr(state), _ptr(xt)))
+        left, counts = [], []
+        for nsteps, valid in calls:
+            running = C.c_int(-1)
+            eng._chk(eng.lib.dm_fmap_fit_steps(eng.ctx, nsteps, B, N1, N2, k1, k2, D, _ptr(e1), k1, _ptr(P2), k2, _ptr(a1), _ptr(A_), _ptr(Bm_),
+                                               _ptr(l1d), _ptr(l2d), None, None, 0, wa, m, _ptr(state), _ptr(xt), _ptr(energy), _ptr(grad),
+                                               2.220446049250313e-09, 1e-5, 15000, maxfun, 20, _ptr(keep_), valid, C.byref(running)))
+            eng._chk(eng.lib.dm_lbfgs_result(eng.ctx, B, n, m, _ptr(state), _ptr(xo), _ptr(fo), _ptr(info)))
+            assert running.value == int((info[:, 0] == 0).sum()), (running.value, info[:, 0].tolist())
+            left.append((xt.clone(), energy.clone(), grad.clone(), state.clone()))
+            counts.append(running.value)
+        return left, counts
+
+    def agree(got, ref):
+        assert len(got) == len(ref)
+        for call, (g, r) in enumerate(zip(got, ref)):
+            assert all(same(u, v) for u, v in zip(g, r)), call
+
+    for weights in (w, wm):
+        # 1. three calls of one step on a keep block (written by the first, read by the others) = three calls that keep nothing = one
+        #    call of three steps
+        plain, _ = fit(weights, A, Bm, e2, x0, [(1, 0)] * 3, None)
+        kept, _ = fit(weights, A, Bm, e2, x0, [(1, 0), (1, 1), (1, 1)], keep)
+        agree(kept, plain)
+        agree(fit(weights, A, Bm, e2, x0, [(3, 0)], keep)[0], plain[2:])
+        assert not same(plain[0][0], plain[2][0])                              # (the optimiser moved)
+        # 2. a fresh start on the same block, other projected descriptors and another basis: rewritten; and back
+        plain2, _ = fit(weights, A2, Bm, e2b, x0, [(1, 0)] * 3, None)
+        agree(fit(weights, A2, Bm, e2b, x0, [(1, 0), (1, 1), (1, 1)], keep)[0], plain2)
+        assert not same(plain2[0][1], plain[0][1])
+        agree(fit(weights, A, Bm, e2, x0, [(1, 0), (1, 1), (1, 1)], keep)[0], plain)
+    # 3. the analytic sums against the oracle's dense indicator
+    E, G = eng.energy_grad(Cs[0], A, Bm, lam1, lam2, wm, e1, e2, a1)
+    for b in range(B):
         ev = orc.ev_sqdiff(lam1[b], lam2[b])
         Eo, Go = orc.energy_grad_general(Cs[0][b], A[b].cpu().numpy().astype(np.float64), Bm[b].cpu().numpy().astype(np.float64), ev,
                                          e1[b].cpu().numpy(), e2[b].cpu().numpy(), a1[b].cpu().numpy(), wm)
-        assert abs(float(plain[0][0][b]) - Eo) <= 1e-11 * abs(Eo)
-        assert np.abs(plain[0][1][b].cpu().numpy() - Go).max() <= 1e-11 * np.abs(Go).max()
-    # the L-BFGS driver sets the option for its own evaluations and hands it back as it found it: a caller's 1 stays 1 (and 0 stays 0)
+        assert abs(float(E[b]) - Eo) <= 1e-11 * abs(Eo)
+        assert np.abs(G[b].cpu().numpy() - Go).max() <= 1e-11 * np.abs(Go).max()
+    # 4. two pairs that stop at different calls: pair 1 (A = Bm = 0, x0 = 0) has a zero gradient at its first evaluation and stops on
+    #    the projected-gradient test at its first advance, pair 0 runs until maxfun = 8; the counts are those of the restated optimiser
+    Az, Bz, xz = A.clone(), Bm.clone(), x0.copy()
+    Az[1], Bz[1], xz[1] = 0.0, 0.0, 0.0
+
+    def restated(b):
+        ev = orc.ev_sqdiff(lam1[b], lam2[b])
+        Ab, Bb = Az[b].cpu().numpy().astype(np.float64), Bz[b].cpu().numpy().astype(np.float64)
+
+        def fg(x, nit=0):
+            Eo, Go = orc.energy_grad_general(x.reshape(k2, k1), Ab, Bb, ev, None, None, None, w)
+            return float(Eo), Go.ravel()
+        return fg
+    ref = lr.drive(None, [restated(0), restated(1)], xz.reshape(B, n), m,
+                   dict(ftol=2.220446049250313e-09, pgtol=1e-5, maxiter=15000, maxfun=8, maxls=20), cap=20)
+    assert ref.stats["knife"] == 0 and ref.nfev.tolist() == [8, 1] and ref.status.tolist() == [lr.MAXFUN, lr.GTOL]
+    expected = [int((ref.nfev > call).sum()) for call in range(1, 9)]          # one evaluation per call: a pair stops at call nfev
+    assert expected == [1] * 7 + [0]
+    _, counts = fit(w, Az, Bz, e2, xz, [(1, 0)] + [(1, 1)] * 7, keep, maxfun=8)
+    assert counts == expected, counts
+    # 5. the option is gone, and the driver of the general fit leaves every option as it found it
+    assert "energy_keep_gram" not in eng.OPTION_DEFAULTS
+    with pytest.raises(ValueError):
+        eng.set_option("energy_keep_gram", 1)
     a2 = torch.as_tensor((rng.uniform(0.5, 1.5, (B, N2)) / N2).astype(np.float32)).to(dev)
     batch = {"Phi1": e1, "Phi2": e2, "a1": a1, "a2": a2, "lam1": lam1, "lam2": lam2,
              "F1": torch.as_tensor(rng.standard_normal((B, N1, D)).astype(np.float32)).to(dev),
              "F2": torch.as_tensor(rng.standard_normal((B, N2, D)).astype(np.float32)).to(dev)}
-    x0 = np.zeros((B, k2, k1))
-    x0[:, 0, 0] = 1.0
-    for value in (1, 0):
-        eng.set_option("energy_keep_gram", value)
-        try:
-            _, res = eng.fit_general(batch, wm, x0, lbfgs_options={"maxfun": 8}, fused=False)
-            assert not hasattr(res, "path")                  # (the driver that sets the option, not the fused fit)
-            assert eng.get_option("energy_keep_gram") == value
-        finally:
-            eng.set_option("energy_keep_gram", 0)
+    before = {q: eng.get_option(q) for q in eng.OPTION_DEFAULTS}
+    _, res = eng.fit_general(batch, wm, x0, lbfgs_options={"maxfun": 8}, fused=False)
+    assert not hasattr(res, "path")                          # (the dm_fmap_fit_steps driver, not the fused fit)
+    assert {q: eng.get_option(q) for q in eng.OPTION_DEFAULTS} == before
 
 
 def test_assignment_from_the_indicator_factors(fx_cfg1, monkeypatch):
