@@ -39,8 +39,8 @@ LIB_EXP = os.path.join(HERE, "libdensematch_exp.so")
 
 
 def build_experiments(force=False, verbose=False):
-    """The same sources with -DDM_EXPERIMENTS: ablation knobs read from the environment (DM_SIMNN_DEBUG, DM_GRED_DEBUG,
-    DM_SOLVE_DEBUG ...), some of which give WRONG results.  Used by tools/*_experiment.py only; a separate file that
+    """The same sources with -DDM_EXPERIMENTS: ablation knobs read from the environment (DM_SIMNN_DEBUG, DM_GRED_DEBUG
+    ...), some of which give WRONG results.  Used by tools/*_experiment.py only; a separate file that
     nothing in the package loads."""
     return build(force=force, verbose=verbose, extra_flags=("-DDM_EXPERIMENTS",), lib=LIB_EXP, objdir=os.path.join(BUILD, "exp"))
 

@@ -733,6 +733,14 @@ constexpr size_t solve_reg_lds(int NBT) {                  // the larger of: the
     const size_t ev = (size_t)4 * dmreg::ev_slot(NBT, solve_reg_ev(NBT), solve_reg_ev(NBT) + 1) * 256 * sizeof(double);
     return img > ev ? img : ev;
 }
+// fmap_solve_kernel: the packed triangle of [M ; rhs], the reduction scratch, four words
+constexpr size_t solve_packed_lds(int n) { return ((size_t)(n + 1) * (n + 2) / 2 + (n + 1 < 16 ? 16 : n + 1) + 4) * sizeof(double); }
+// fmap_solve_blocked_kernel: NB (NB + 1) / 2 + 2 blocks of 2 KiB (triangle, LT, Ws), rhs and xv, invp, red
+constexpr size_t solve_blocked_lds(int NB) { return ((size_t)(NB * (NB + 1) / 2 + 2) * 256 + 2 * NB * 16 + 16 + 8) * sizeof(double); }
+// fmap_solve_2phase_kernel: the resident blocks of phase 1 (NA leading block rows) + LT, Ws; rhs and xv, red; blk, cstart, tri_rc
+constexpr size_t solve_2phase_lds(int NB, int NA) {
+    return ((size_t)(NA * (NA + 1) / 2 + (NB - NA) * NA + 2) * 256 + 2 * NB * 16 + 8) * sizeof(double) + (96 + 16 + 128) * sizeof(int);
+}
 
 template <int NBT>
 __global__ __launch_bounds__(256, 1) void fmap_solve_reg_kernel(const double* __restrict__ PQ, const double* __restrict__ Timg,
@@ -846,146 +854,163 @@ __global__ __launch_bounds__(256, 1) void fmap_solve_reg_kernel(const double* __
     if (lane == 0) Crow[0] = ci0;
 }
 
-// workspace of the closed-form solve (fmap_solve_core)
-static size_t fmap_solve_ws(const dm_ctx* ctx, int B, int k1, int k2) {
-    const size_t pq_bytes = (size_t)B * (k1 + k2) * k1 * 8;
-    const int n = k1 - 1, NB = (n + 15) / 16;
-    const bool two_phase = (NB == 12 || NB == 13) && !ctx->opt_solve_packed;
-    const bool blocked = ((n >= 1 && NB <= 11) && !ctx->opt_solve_packed) || two_phase;
-    const size_t img_bytes = blocked ? (size_t)B * (NB * (NB + 1) / 2) * 256 * 8 : 0;
-    const int NA = (NB + 1) / 2, grid2 = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    const size_t spill_bytes = two_phase ? (size_t)grid2 * (NA * (NA + 1) / 2) * 256 * 8 : 0;
-    const size_t pcgs_bytes = (ctx->opt_solve_pcg && n > 128 && n <= 256) ? pcgs_image_bytes(B, n) : 0;
-    return dm_align_up(pq_bytes) + dm_align_up(img_bytes) + dm_align_up(spill_bytes) + dm_align_up((size_t)B * dm_cdiv(k2, 32) * 4) + dm_align_up(pcgs_bytes) + 4096;
+// =================================================================================================
+// Host side of the closed-form solve.  ONE plan per call says which kernels run and what each of them needs: the reserve
+// (fmap_solve_ws) and the launches (fmap_solve_core) both read it, neither restates a size, a route condition or an LDS formula.
+// =================================================================================================
+enum fmap_direct { FMAP_REG, FMAP_BLOCKED, FMAP_2PHASE, FMAP_PACKED }; // the direct solver (launch name "fmap_solve_chol")
+enum fmap_iter { FMAP_ITER_NONE, FMAP_ITER_SMALL, FMAP_ITER_BIG };     // the batched iteration in front of it ("fmap_solve_pcg")
+
+struct fmap_solve_plan {
+    int n, NB;                     // unknowns per system (k1 - 1) and the 16-row blocks of its matrix
+    int NA, grid2;                 // two-phase solver: leading block rows of phase 1, persistent workgroups
+    int ngroups;                   // groups of PCG_NS systems per pair: the iteration's workgroups and fall-back flag words per pair
+    fmap_direct direct;
+    int NBT;                       // FMAP_REG: block rows of the instantiation (2, 4, 6, 8)
+    fmap_iter iter;
+    // the arena pieces in take order; 0: the route does not use the piece, it is not taken
+    size_t pq_bytes;               // P and Q of every pair
+    size_t timg_bytes;             // P[1:, 1:] of every pair as the 16 x 16 blocks the direct solvers read (OutScaled::img),
+    long long timg_stride;         //   timg_stride doubles per pair
+    size_t spill_bytes;            // two-phase solver: L11 of every resident workgroup
+    size_t flag_bytes;             // iteration: the fall-back flag words
+    size_t stream_bytes;           // big iteration: the matrix fragments it streams (pcgs_pack_kernel)
+    size_t lds_direct, lds_iter;   // dynamic LDS of the two kernels
+};
+
+// The solver is chosen by the SIZES alone, never by the batch: a pair's bits do not depend on the batch it is in.  (Measured and not
+// adopted: the iteration costs ~125 us at n = 127 / ~330 us at n = 199 whatever the batch, the direct solvers 52 / 98 us for ONE pair --
+// they win below 16-24 pairs of k = 128 and below 4 pairs of k = 200, profiles/r06_solve_pcg_crossover.txt -- but a switch on B k2
+// makes the map of a pair solved alone differ by 5e-12 from the same pair in a batch of 64.)
+static fmap_solve_plan fmap_solve_plan_for(const dm_ctx* ctx, int B, int k1, int k2) {
+    fmap_solve_plan p{};
+    const int n = p.n = k1 - 1;
+    const int NB = p.NB = (n + 15) / 16;                  // (the entry points require k1 <= 200: NB <= 13)
+    p.NA = (NB + 1) / 2;
+    p.grid2 = ctx->n_cu > 0 ? ctx->n_cu : 256;
+    p.ngroups = dm_cdiv(k2, PCG_NS);
+    // the packed-storage solver: dm_set_option("solve_packed", 1) (tests), and n = 0 (k1 = 1), where only the pinned column is written
+    p.direct = (ctx->opt_solve_packed || n == 0) ? FMAP_PACKED
+               : NB >= 12 ? FMAP_2PHASE                   // 177 <= n: the block triangle does not fit the LDS
+               : (NB <= 8 && ctx->opt_solve_reg) ? FMAP_REG : FMAP_BLOCKED;
+    p.NBT = p.direct != FMAP_REG ? 0 : NB <= 2 ? 2 : NB <= 4 ? 4 : NB <= 6 ? 6 : 8;
+    // the iteration: systems of order 65 .. 128 in front of the register solver (one instantiation: eight row tiles on four waves; whole
+    // workgroups of the direct solver must belong to one pair for its fall-back launch: k2 % 4 == 0), of order 129 .. 199 with streamed
+    // matrix fragments in front of the LDS solvers
+    p.iter = !ctx->opt_solve_pcg ? FMAP_ITER_NONE
+             : (p.direct == FMAP_REG && n >= 65 && k2 % 4 == 0) ? FMAP_ITER_SMALL
+             : (p.direct != FMAP_REG && p.direct != FMAP_PACKED && NB >= 9) ? FMAP_ITER_BIG : FMAP_ITER_NONE;
+    p.pq_bytes = (size_t)B * (k1 + k2) * k1 * 8;
+    p.timg_stride = p.direct == FMAP_PACKED ? 0 : (long long)NB * (NB + 1) / 2 * 256;
+    p.timg_bytes = (size_t)B * p.timg_stride * 8;
+    p.spill_bytes = p.direct == FMAP_2PHASE ? (size_t)p.grid2 * (p.NA * (p.NA + 1) / 2) * 256 * 8 : 0;
+    p.flag_bytes = p.iter != FMAP_ITER_NONE ? (size_t)B * p.ngroups * 4 : 0;
+    p.stream_bytes = p.iter == FMAP_ITER_BIG ? pcgs_image_bytes(B, n) : 0;
+    p.lds_direct = p.direct == FMAP_REG ? solve_reg_lds(p.NBT) : p.direct == FMAP_BLOCKED ? solve_blocked_lds(NB)
+                   : p.direct == FMAP_2PHASE ? solve_2phase_lds(NB, p.NA) : solve_packed_lds(n);
+    p.lds_iter = p.iter == FMAP_ITER_SMALL ? pcg_lds_bytes(8, 4) : p.iter == FMAP_ITER_BIG ? pcg_lds_bytes(PCGS_NT, PCGS_NW) : 0;
+    return p;
 }
 
-// the batched iteration (dm_pcg.h) takes the systems of order 65 .. 128 (one instantiation: eight row tiles on four waves); whole
-// workgroups of the direct solver must belong to one pair for its fall-back launch (k2 % 4 == 0)
-static inline bool fmap_solve_pcg_ok(const dm_ctx* ctx, int k1, int k2) {
-    const int n = k1 - 1;
-    return ctx->opt_solve_pcg && ctx->opt_solve_reg && !ctx->opt_solve_packed && n >= 65 && n <= 128 && k2 % 4 == 0;
+// workspace of the closed-form solve: what fmap_solve_core takes (dm_ws_take starts every piece on a multiple of 256)
+static size_t fmap_solve_ws(const fmap_solve_plan& p) {
+    return dm_align_up(p.pq_bytes) + dm_align_up(p.timg_bytes) + dm_align_up(p.spill_bytes) + dm_align_up(p.flag_bytes) + dm_align_up(p.stream_bytes);
 }
 
 // Gram matrices + the k2 solves per pair; OPA = the stacked rows [A; Bm], OPB = the rows of A (fp32 arrays, or the split-K
-// partials of the projections: dm_gemm_f64.h).  Workspace from what the caller reserved (fmap_solve_ws).
+// partials of the projections: dm_gemm_f64.h).  `p` = fmap_solve_plan_for the same sizes; workspace from what the caller reserved
+// (fmap_solve_ws).
 template <class OPA, class OPB>
-static int fmap_solve_core(dm_ctx* ctx, int B, int k1, int k2, int D, const OPA& opa, const OPB& opb,
+static int fmap_solve_core(dm_ctx* ctx, const fmap_solve_plan& p, int B, int k1, int k2, int D, const OPA& opa, const OPB& opb,
                            const double* lam1, const double* lam2, const double* c00, double w_descr, double w_lap,
                            double* C, int32_t* info) {
-    const size_t pq_bytes = (size_t)B * (k1 + k2) * k1 * 8;
-    const int n = k1 - 1;
-    const int NB = (n + 15) / 16;
-    const bool two_phase = (NB == 12 || NB == 13) && !ctx->opt_solve_packed;   // 177 <= n <= 208
-    const bool blocked = ((n >= 1 && NB <= 11) && !ctx->opt_solve_packed) || two_phase;   // dm_set_option("solve_packed", 1): tests
-    const size_t img_bytes = blocked ? (size_t)B * (NB * (NB + 1) / 2) * 256 * 8 : 0;
-    const int NA = (NB + 1) / 2;
-    const int grid2 = ctx->n_cu > 0 ? ctx->n_cu : 256;
-    const size_t spill_bytes = two_phase ? (size_t)grid2 * (NA * (NA + 1) / 2) * 256 * 8 : 0;
-    int rc = DM_OK;
-    double* PQ = (double*)dm_ws_take(ctx, pq_bytes);
-    double* Timg = blocked ? (double*)dm_ws_take(ctx, img_bytes) : nullptr;
-    double* spill = two_phase ? (double*)dm_ws_take(ctx, spill_bytes) : nullptr;
-    if (!PQ || (blocked && !Timg) || (two_phase && !spill)) return dm_fail(ctx, DM_ENOMEM, "fmap_solve: workspace not reserved");
-    if (blocked) DM_CHECK_HIP(ctx, hipMemsetAsync(Timg, 0, img_bytes, ctx->stream));
-    // The solver is chosen by the SIZES alone, never by the batch: a pair's bits do not depend on the batch it is in.  (Measured and not
-    // adopted: the iteration costs ~125 us at n = 127 / ~330 us at n = 199 whatever the batch, the direct solvers 52 / 98 us for ONE pair --
-    // they win below 16-24 pairs of k = 128 and below 4 pairs of k = 200, profiles/r06_solve_pcg_crossover.txt -- but a switch on B k2
-    // makes the map of a pair solved alone differ by 5e-12 from the same pair in a batch of 64.)
-    const bool pcg_small = blocked && !two_phase && NB <= 8 && ctx->opt_solve_reg && fmap_solve_pcg_ok(ctx, k1, k2);
-    const bool pcg_big = (two_phase || (blocked && NB >= 9)) && ctx->opt_solve_pcg && !ctx->opt_solve_packed;
+    const int n = p.n, NB = p.NB;
+    bool reserved = true;
+    auto take = [&](size_t bytes) -> void* {
+        void* q = bytes ? dm_ws_take(ctx, bytes) : nullptr;
+        reserved = reserved && (q || !bytes);
+        return q;
+    };
+    double* PQ = (double*)take(p.pq_bytes);
+    double* Timg = (double*)take(p.timg_bytes);
+    double* spill = (double*)take(p.spill_bytes);
+    int32_t* fb = (int32_t*)take(p.flag_bytes);
+    double* img = (double*)take(p.stream_bytes);
+    if (!reserved) return dm_fail(ctx, DM_ENOMEM, "fmap_solve: workspace not reserved");
+    if (Timg) DM_CHECK_HIP(ctx, hipMemsetAsync(Timg, 0, p.timg_bytes, ctx->stream));
     // (with the batched iteration in front, its group-0 workgroups clear the status words: one memset launch less per call)
-    if (!pcg_small && !pcg_big) DM_CHECK_HIP(ctx, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), ctx->stream));
+    if (p.iter == FMAP_ITER_NONE) DM_CHECK_HIP(ctx, hipMemsetAsync(info, 0, (size_t)B * sizeof(int32_t), ctx->stream));
 
-    OutScaled out{PQ, (long long)(k1 + k2) * k1, k1, w_descr, Timg, (long long)(NB * (NB + 1) / 2) * 256, k1};
-    dim3 grid(dm_cdiv(k1 + k2, NT_T) * dm_cdiv(k1, NT_T), 1, B);
-    switch (dm_knob("DM_GRAM_NPRE", 2)) {           // experiments: stages of operand loads in flight (96 -> 71 us with the uniform fast path of the operand functors; 1 / 2 / 3 / 4 stages: 73.5 / 71.4 / 73.6 / 75.1)
-        case 1: DM_LAUNCH(ctx, "gram_nt_f64", (gemm_nt_f64<OPA, OPB, OutScaled, 1>), grid, dim3(256), 0, opa, opb, out, k1 + k2, k1, D); break;
-        case 4: DM_LAUNCH(ctx, "gram_nt_f64", (gemm_nt_f64<OPA, OPB, OutScaled, 4>), grid, dim3(256), 0, opa, opb, out, k1 + k2, k1, D); break;
-        case 3: DM_LAUNCH(ctx, "gram_nt_f64", (gemm_nt_f64<OPA, OPB, OutScaled, 3>), grid, dim3(256), 0, opa, opb, out, k1 + k2, k1, D); break;
-        default: DM_LAUNCH(ctx, "gram_nt_f64", (gemm_nt_f64<OPA, OPB, OutScaled, 2, true>), dim3(grid.x * (unsigned)B), dim3(256), 0, opa, opb, out, k1 + k2, k1, D); break;
-    }
+    OutScaled out{PQ, (long long)(k1 + k2) * k1, k1, w_descr, Timg, p.timg_stride, k1};
+    const unsigned tiles = (unsigned)(dm_cdiv(k1 + k2, NT_T) * dm_cdiv(k1, NT_T));
+    // two stages of operand loads in flight (96 -> 71 us with the uniform fast path of the operand functors; 1 / 2 / 3 / 4 stages: 73.5 / 71.4 / 73.6 / 75.1)
+    DM_LAUNCH(ctx, "gram_nt_f64", (gemm_nt_f64<OPA, OPB, OutScaled, 2, true>), dim3(tiles * (unsigned)B), dim3(256), 0, opa, opb, out, k1 + k2, k1, D);
 
-    const int32_t* only_if_big = nullptr;
-    const int only_ng = dm_cdiv(k2, PCG_NS);
-    if (pcg_big) {
-        // r06: systems of order 129 .. 208 by the batched iteration with STREAMED matrix fragments (dm_pcg.h: fmap_solve_pcgs_kernel); the
-        // LDS solvers below then only run the pairs it flagged
-        int32_t* fb = (int32_t*)dm_ws_take(ctx, (size_t)B * only_ng * 4);
-        double* img = (double*)dm_ws_take(ctx, pcgs_image_bytes(B, n));
-        if (!fb || !img) return dm_fail(ctx, DM_ENOMEM, "fmap_solve: workspace not reserved");
-        const int NTp = (n + 15) / 16, KSP = pcgs_ksp(n), ngroups = dm_cdiv(k2, PCG_NS);
-        DM_LAUNCH(ctx, "fmap_solve_pcg_pack", pcgs_pack_kernel, dim3(64, B), dim3(256), 0, (const double*)PQ, k1, k2, NTp, KSP, img);
-        const size_t lds_pcg = pcg_lds_bytes(PCGS_NT, PCGS_NW);
-        rc = dm_grant_lds(ctx, (const void*)fmap_solve_pcgs_kernel, lds_pcg);
-        if (rc) return rc;
-        DM_LAUNCH(ctx, "fmap_solve_pcg", fmap_solve_pcgs_kernel, dim3((unsigned)(B * ngroups)), dim3(64 * PCGS_NW), lds_pcg, (const double*)PQ,
-                  (const double*)img, lam1, lam2, c00, w_lap, k1, k2, ngroups, NTp, KSP, 1e-22, 48, 6, 3e-4, C, fb, info);
-        only_if_big = fb;
-    }
-    if (two_phase) {
-        const int NBr = NB - NA;
-        const size_t lds = ((size_t)(NA * (NA + 1) / 2 + NBr * NA + 2) * 256 + 2 * NB * 16 + 8) * sizeof(double) + (96 + 16 + 128) * sizeof(int);
-        rc = dm_grant_lds(ctx, (const void*)fmap_solve_2phase_kernel, lds);
-        if (rc) return rc;
-        const long long nsys = (long long)B * k2;
-        DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_2phase_kernel, dim3((unsigned)(nsys < grid2 ? nsys : grid2)), dim3(256), lds, PQ, Timg,
-                  lam1, lam2, c00, w_lap, k1, k2, NB, B, spill, C, info, only_if_big, only_ng);
-        return DM_OK;
-    }
-    if (blocked && !two_phase && NB <= 8 && ctx->opt_solve_reg) {
-        // register-resident solver: one wave per system, four systems per CU (dm_chol_reg.h)
-        const long long nsys = (long long)B * k2;
-        const dim3 grid((unsigned)((nsys + 3) / 4));
-        const int32_t* only_if = nullptr;
-        if (pcg_small) {
-            // r06: the batched Jacobi-preconditioned conjugate-gradient iteration first (dm_pcg.h); the direct solver below then only
-            // runs the pairs whose iteration did not converge or met a non-positive curvature (its workgroups of the other pairs leave
-            // at once)
-            int32_t* fb = (int32_t*)dm_ws_take(ctx, (size_t)B * only_ng * 4);
-            if (!fb) return dm_fail(ctx, DM_ENOMEM, "fmap_solve: workspace not reserved");
-            const int ngroups = dm_cdiv(k2, PCG_NS);
-            const size_t lds_pcg = pcg_lds_bytes(8, 4);
-            rc = dm_grant_lds(ctx, (const void*)fmap_solve_pcg_kernel<8, 4>, lds_pcg);
+    // the iteration first; the direct solver below then only runs the pairs it flagged in `fb`: those whose iteration did not converge or
+    // met a non-positive curvature (its workgroups of the other pairs leave at once).  The stopping rule: dm_pcg.h
+    int rc = DM_OK;
+    const dim3 grid_iter((unsigned)(B * p.ngroups));
+    switch (p.iter) {
+        case FMAP_ITER_NONE: break;
+        case FMAP_ITER_SMALL:
+            // r06: the batched Jacobi-preconditioned conjugate-gradient iteration, the matrix in registers (dm_pcg.h)
+            rc = dm_grant_lds(ctx, (const void*)fmap_solve_pcg_kernel<8, 4>, p.lds_iter);
             if (rc) return rc;
-            // stop at a relative reduction of 1e-22 of the recurrence's r^T M^-1 r (1e-11 in that norm: the iterate is within ~1e-10 of
-            // the direct solution at cond = 1e2; at condition number kappa the distance grows with kappa: <= max(1e-9, 4 (n + D) u kappa)
-            // relative, u = 2^-53, tests/test_gpu_solver_conditioning.py; the bar on C is 1e-4, the closed form's own distance to the
-            // float64 minimiser 6e-8); at most 48 steps, and a pair whose reduction is still above 3e-4 after 6 goes to the direct solver at once (measured on three
-            // descriptor families x three weightings, profiles/r06_solver_jacobi_pcg_experiment.txt: <= 4.7e-5 after six steps where
-            // the iteration finishes in 20 - 29, >= 2.4e-3 for rank-deficient descriptors, which would need more than 48)
-            DM_LAUNCH(ctx, "fmap_solve_pcg", (fmap_solve_pcg_kernel<8, 4>), dim3((unsigned)(B * ngroups)), dim3(256), lds_pcg, PQ, lam1, lam2, c00,
-                      w_lap, k1, k2, ngroups, 1e-22, 48, 6, 3e-4, C, fb, info);
-            only_if = fb;
+            DM_LAUNCH(ctx, "fmap_solve_pcg", (fmap_solve_pcg_kernel<8, 4>), grid_iter, dim3(256), p.lds_iter, PQ, lam1, lam2, c00,
+                      w_lap, k1, k2, p.ngroups, PCG_TOL2, PCG_MAXIT, PCG_SLOW_IT, PCG_SLOW_TOL2, C, fb, info);
+            break;
+        case FMAP_ITER_BIG: {
+            // r06: the same iteration with STREAMED matrix fragments (dm_pcg.h: fmap_solve_pcgs_kernel)
+            const int KSP = pcgs_ksp(n);
+            DM_LAUNCH(ctx, "fmap_solve_pcg_pack", pcgs_pack_kernel, dim3(64, B), dim3(256), 0, (const double*)PQ, k1, k2, NB, KSP, img);
+            rc = dm_grant_lds(ctx, (const void*)fmap_solve_pcgs_kernel, p.lds_iter);
+            if (rc) return rc;
+            DM_LAUNCH(ctx, "fmap_solve_pcg", fmap_solve_pcgs_kernel, grid_iter, dim3(64 * PCGS_NW), p.lds_iter, (const double*)PQ,
+                      (const double*)img, lam1, lam2, c00, w_lap, k1, k2, p.ngroups, NB, KSP, PCG_TOL2, PCG_MAXIT, PCG_SLOW_IT, PCG_SLOW_TOL2, C, fb, info);
+            break;
         }
+    }
+
+    const int32_t* only_if = fb;             // (null without an iteration: every pair)
+    const long long nsys = (long long)B * k2;
+    switch (p.direct) {
+        case FMAP_REG: {
+            // register-resident solver: one wave per system, four systems per CU (dm_chol_reg.h)
+            const dim3 grid((unsigned)((nsys + 3) / 4));
 #define DM_SOLVE_REG(NBT_)                                                                                             \
-        {                                                                                                              \
-            rc = dm_grant_lds(ctx, (const void*)fmap_solve_reg_kernel<NBT_>, solve_reg_lds(NBT_));                     \
-            if (rc) return rc;                                                                                         \
-            DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_reg_kernel<NBT_>, grid, dim3(256), solve_reg_lds(NBT_), PQ, Timg, lam1, lam2, \
-                      c00, w_lap, k1, k2, NB, nsys, C, info, only_if, only_ng);                                        \
-        }
-        if (NB <= 2) DM_SOLVE_REG(2)
-        else if (NB <= 4) DM_SOLVE_REG(4)
-        else if (NB <= 6) DM_SOLVE_REG(6)
-        else DM_SOLVE_REG(8)
+            {                                                                                                          \
+                rc = dm_grant_lds(ctx, (const void*)fmap_solve_reg_kernel<NBT_>, p.lds_direct);                        \
+                if (rc) return rc;                                                                                     \
+                DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_reg_kernel<NBT_>, grid, dim3(256), p.lds_direct, PQ, Timg, lam1, lam2, \
+                          c00, w_lap, k1, k2, NB, nsys, C, info, only_if, p.ngroups);                                  \
+            }
+            if (p.NBT == 2) DM_SOLVE_REG(2)
+            else if (p.NBT == 4) DM_SOLVE_REG(4)
+            else if (p.NBT == 6) DM_SOLVE_REG(6)
+            else DM_SOLVE_REG(8)
 #undef DM_SOLVE_REG
-        return DM_OK;
+            break;
+        }
+        case FMAP_BLOCKED:
+            // blocked MFMA solver: one workgroup per system, the block triangle in LDS
+            rc = dm_grant_lds(ctx, (const void*)fmap_solve_blocked_kernel, p.lds_direct);
+            if (rc) return rc;
+            DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_blocked_kernel, dim3(k2, B), dim3(256), p.lds_direct, PQ, Timg, lam1, lam2, c00,
+                      w_lap, k1, k2, NB, C, info, only_if, p.ngroups);
+            break;
+        case FMAP_2PHASE:
+            rc = dm_grant_lds(ctx, (const void*)fmap_solve_2phase_kernel, p.lds_direct);
+            if (rc) return rc;
+            DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_2phase_kernel, dim3((unsigned)(nsys < p.grid2 ? nsys : p.grid2)), dim3(256), p.lds_direct, PQ, Timg,
+                      lam1, lam2, c00, w_lap, k1, k2, NB, B, spill, C, info, only_if, p.ngroups);
+            break;
+        case FMAP_PACKED:
+            rc = dm_grant_lds(ctx, (const void*)fmap_solve_kernel, p.lds_direct);
+            if (rc) return rc;
+            DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_kernel, dim3(k2, B), dim3(SP_NT), p.lds_direct, PQ, lam1, lam2, c00, w_lap, k1, k2,
+                      C, info, 0 /* dbg: no phase disabled */);
+            break;
     }
-    if (blocked) {
-        // blocked MFMA solver: NB(NB+1)/2 + 2 blocks of 2 KiB, vectors
-        const size_t lds = ((size_t)(NB * (NB + 1) / 2 + 2) * 256 + 2 * NB * 16 + 16 + 8) * sizeof(double);
-        rc = dm_grant_lds(ctx, (const void*)fmap_solve_blocked_kernel, lds);
-        if (rc) return rc;
-        DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_blocked_kernel, dim3(k2, B), dim3(256), lds, PQ, Timg, lam1, lam2, c00,
-                  w_lap, k1, k2, NB, C, info, only_if_big, only_ng);
-        return DM_OK;
-    }
-    const size_t lds = ((size_t)(n + 1) * (n + 2) / 2 + (n + 1 < 16 ? 16 : n + 1) + 4) * sizeof(double);
-    rc = dm_grant_lds(ctx, (const void*)fmap_solve_kernel, lds);
-    if (rc) return rc;
-    // DM_EXPERIMENTS builds only: 1 no trailing update, 2 no back substitution, 3 no factorisation (wrong results)
-    DM_LAUNCH(ctx, "fmap_solve_chol", fmap_solve_kernel, dim3(k2, B), dim3(SP_NT), lds, PQ, lam1, lam2, c00, w_lap, k1, k2,
-              C, info, dm_knob("DM_SOLVE_DEBUG", 0));
     return DM_OK;
 }
 
@@ -998,11 +1023,12 @@ extern "C" int dm_fmap_solve(dm_ctx* ctx, int B, int k1, int k2, int D, const fl
     DM_REQUIRE(ctx, k1 <= 200, "k1 > 200 does not fit the in-LDS solver");
     DM_REQUIRE(ctx, w_descr >= 0.0 && w_lap >= 0.0 && (w_descr > 0.0 || w_lap > 0.0), "weights must be >= 0 and not both 0");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = dm_ws_reserve(ctx, fmap_solve_ws(ctx, B, k1, k2));
+    const fmap_solve_plan plan = fmap_solve_plan_for(ctx, B, k1, k2);
+    int rc = dm_ws_reserve(ctx, fmap_solve_ws(plan));
     if (rc) return rc;
     KRowsStackedF32 opa{A, Bm, k1, k2, D};
     KRowsF32 opb{A, (long long)k1 * D, D, k1, D};
-    return fmap_solve_core(ctx, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
+    return fmap_solve_core(ctx, plan, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
 }
 
 // =================================================================================================
@@ -1020,8 +1046,9 @@ static int fmap_fit_impl(dm_ctx* ctx, int B, int N1, int N2, int D, int k1, int 
     DM_REQUIRE(ctx, w_descr >= 0.0 && w_lap >= 0.0 && (w_descr > 0.0 || w_lap > 0.0), "weights must be >= 0 and not both 0");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bA = (size_t)B * k1 * D * 4, bB = (size_t)B * k2 * D * 4;
+    const fmap_solve_plan plan = fmap_solve_plan_for(ctx, B, k1, k2);
     int rc = dm_ws_reserve(ctx, dm_project_f16split_ws(B, N1, D, k1, ld1, (int)sizeof(TR)) + dm_project_f16split_ws(B, N2, D, k2, ld2, (int)sizeof(TR)) +
-                                    dm_align_up(bA) + dm_align_up(bB) + dm_align_up((size_t)B * 8) + fmap_solve_ws(ctx, B, k1, k2) + 8192);
+                                    dm_align_up(bA) + dm_align_up(bB) + dm_align_up((size_t)B * 8) + fmap_solve_ws(plan) + 8192);
     if (rc) return rc;
     double* c00 = (double*)dm_ws_take(ctx, (size_t)B * 8);
     if (!c00) return dm_fail(ctx, DM_ENOMEM, "fmap_fit: workspace not reserved");
@@ -1043,11 +1070,11 @@ static int fmap_fit_impl(dm_ctx* ctx, int B, int N1, int N2, int D, int k1, int 
         const long long sA = nsA == 2 ? (long long)B * k1 * D : 0, sB = nsB == 2 ? (long long)B * k2 * D : 0;
         KRowsStackedPart opa{pA, pB, sA, sB, k1, k2, D};
         KRowsPart opb{pA, sA, k1, D};
-        return fmap_solve_core(ctx, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
+        return fmap_solve_core(ctx, plan, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
     }
     KRowsStackedF32 opa{A, Bm, k1, k2, D};
     KRowsF32 opb{A, (long long)k1 * D, D, k1, D};
-    return fmap_solve_core(ctx, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
+    return fmap_solve_core(ctx, plan, B, k1, k2, D, opa, opb, lam1, lam2, c00, w_descr, w_lap, C, info);
 }
 extern "C" int dm_fmap_fit(dm_ctx* ctx, int B, int N1, int N2, int D, int k1, int k2, const float* Phi1, int ld1, const float* Phi2,
                            int ld2, const float* mass1, const float* mass2, const void* F1, const void* F2, const double* lam1,

@@ -40,6 +40,16 @@ constexpr int PCG_LDP = 48;       // LDS row stride (doubles) of the direction b
 
 static inline size_t pcg_lds_bytes(int NT, int NW) { return ((size_t)NT * 16 * PCG_LDP + 2 * NW * PCG_NS + 64) * sizeof(double); }
 
+// The stopping rule both iteration kernels are launched with (their arguments tol2, maxit, slow_it, slow_tol2):
+// stop at a relative reduction of 1e-22 of the recurrence's r^T M^-1 r (1e-11 in that norm: the iterate is within ~1e-10 of
+// the direct solution at cond = 1e2; at condition number kappa the distance grows with kappa: <= max(1e-9, 4 (n + D) u kappa)
+// relative, u = 2^-53, tests/test_gpu_solver_conditioning.py; the bar on C is 1e-4, the closed form's own distance to the
+// float64 minimiser 6e-8); at most 48 steps, and a pair whose reduction is still above 3e-4 after 6 goes to the direct solver at once (measured on three
+// descriptor families x three weightings, profiles/r06_solver_jacobi_pcg_experiment.txt: <= 4.7e-5 after six steps where
+// the iteration finishes in 20 - 29, >= 2.4e-3 for rank-deficient descriptors, which would need more than 48)
+constexpr double PCG_TOL2 = 1e-22, PCG_SLOW_TOL2 = 3e-4;
+constexpr int PCG_MAXIT = 48, PCG_SLOW_IT = 6;
+
 // sum over the rows of a column (= over a system's unknowns) of the per-lane partials v[ct]: across the lane's four row groups by
 // shuffles, across the waves through `red` (NW x 32 doubles), every lane ends with the totals of its two columns, added in wave order
 // sum over the four 16-lane rows of a wave, the same total (and the same order of additions) in every row: (row 0 + row 1) + (row 2 + row 3).

@@ -2,7 +2,7 @@
 GPU (-m gpu): the closed-form solver (dm_fmap_solve / dm_fmap_fit) on ILL-CONDITIONED systems, every route.
 
 Row i of C solves (P_ff + diag(dd_i)) x_i = rhs_i (oracle.dm_oracle.fmap_solve).  The library picks its solver by the sizes and the
-options alone (dm_fmap.hip: fmap_solve_core), n = k1 - 1:
+options alone (dm_fmap.hip: fmap_solve_plan_for), n = k1 - 1:
 
     n <= 64                                 fmap_solve_reg_kernel<NBT>
     65 <= n <= 128, k2 % 4 == 0             fmap_solve_pcg_kernel<8, 4>, fall-back fmap_solve_reg_kernel<8>   (solve_pcg)
@@ -387,3 +387,78 @@ def test_conditioning_fit_isometric_torus(eng, real_dtype):
     err = np.abs(Cf[0] - Co).max()
     print(f"isometric torus {np.dtype(real_dtype).name}: kappa max {kappa.max():.2e}, |C - C_oracle| = {err:.2e}, fell back: {fell_back[0]}")
     assert err <= 1e-4
+
+
+@pytest.mark.parametrize("k2", [1, 5])
+def test_single_column_map_is_the_pinned_column(eng, k2):
+    """k1 = 1 leaves no system to solve: C is the pinned column (c00 in row 0, exact zeros below), info = 0, the same bits on a
+    second call -- through fmap_solve and through fmap_fit.  Whichever direct kernel writes it: no iteration runs"""
+    B, D, N = 2, 16, 64
+    rng = np.random.default_rng(40 + k2)
+    A = (rng.standard_normal((B, 1, D)) * 0.1).astype(np.float32)
+    Bm = (rng.standard_normal((B, k2, D)) * 0.1).astype(np.float32)
+    lam1 = np.zeros((B, 1))
+    lam2 = np.sort(rng.uniform(0.0, 4.0, (B, k2)), axis=1); lam2[:, 0] = 0.0
+    c00 = _c00(B)
+    want = np.zeros((B, k2, 1)); want[:, 0, 0] = c00
+    C, info, kern = solve(eng, A, Bm, lam1, lam2, c00, WD, WL, {})
+    assert len(kern.get("fmap_solve_chol", ())) == 1 and "fmap_solve_pcg" not in kern, kern
+    assert np.array_equal(C, want) and not np.signbit(C[:, 1:]).any() and np.all(info == 0), (C, info)
+    C2, info2, _ = solve(eng, A, Bm, lam1, lam2, c00, WD, WL, {})
+    assert C2.tobytes() == C.tobytes() and np.all(info2 == 0)
+
+    Phi1 = (rng.standard_normal((B, N, 8)) * 0.1).astype(np.float32)          # (row stride 8; the fit reads lam's k1 = 1, k2 columns)
+    Phi2 = (rng.standard_normal((B, N, 8)) * 0.1).astype(np.float32)
+    a1 = rng.uniform(0.5, 1.5, (B, N)).astype(np.float32) / N
+    a2 = rng.uniform(0.5, 1.5, (B, N)).astype(np.float32) / N
+    F1 = rng.standard_normal((B, N, D)).astype(np.float16)
+    F2 = rng.standard_normal((B, N, D)).astype(np.float16)
+    want[:, 0, 0] = eng.c00(Phi1, Phi2, a1, a2).cpu().numpy()
+    assert np.all(want[:, 0, 0] != 0.0)
+    Cf = eng.fmap_fit(Phi1, Phi2, a1, a2, F1, F2, lam1, lam2, WD, WL).cpu().numpy()
+    assert np.array_equal(Cf, want) and not np.signbit(Cf[:, 1:]).any(), Cf
+    Cf2 = eng.fmap_fit(Phi1, Phi2, a1, a2, F1, F2, lam1, lam2, WD, WL).cpu().numpy()
+    assert Cf2.tobytes() == Cf.tobytes()
+
+
+# dm_workspace_bytes after ONE fmap_solve (B = 4, D = 2 k1) on a fresh engine at commit 6252592, which reserved the streamed image and the
+# flag words on every route plus 4096 bytes of slack; the plan reserves what it takes, never more
+ARENA_BYTES_BEFORE_THE_PLAN = {(17, 17): 1048576, (128, 128): 2097152, (150, 20): 2097152, (194, 24): 18874368}
+
+
+@pytest.mark.parametrize("k1,k2", sorted(ARENA_BYTES_BEFORE_THE_PLAN))
+def test_arena_no_larger_than_before_the_plan(k1, k2):
+    from densematcher_amd.engine import MatchEngine
+    B, D = 4, 2 * k1
+    A, Bm, lam1, lam2 = _stack([make_pair("well", k1, k2, D, 1000 * k1 + k2 + q) for q in range(B)])
+    fresh = MatchEngine()
+    try:
+        fresh.fmap_solve(A, Bm, lam1, lam2, _c00(B), WD, WL)
+        got = fresh.workspace_bytes()
+    finally:
+        fresh.close()
+    print(f"arena after one fmap_solve, k1 = {k1}, k2 = {k2}: {got} bytes (before the plan: {ARENA_BYTES_BEFORE_THE_PLAN[(k1, k2)]})")
+    assert 0 < got <= ARENA_BYTES_BEFORE_THE_PLAN[(k1, k2)]
+
+
+ARENA_SMALL_ROUTE_BEFORE_THE_PLAN = 2097152      # measured at commit 6252592 with the call below
+
+
+def test_arena_small_route_reserves_what_it_takes():
+    """a batch sized so that any over-reservation shows: k1 = k2 = 17, B = 156 takes P, Q (156 * 34 * 17 * 8 -> 721408 bytes in
+    multiples of 256) and the block image (156 * 2048 = 319488), 1040896 in all; dm_ws_reserve adds 4096 and rounds to 1 MiB, which
+    leaves 3584 bytes: the slack and the flag words reserved on this route at commit 6252592 (4096 + 768) made it 2 MiB there"""
+    from densematcher_amd.engine import MatchEngine
+    k, B, D = 17, 156, 34
+    rng = np.random.default_rng(17156)
+    A = (rng.standard_normal((B, k, D)) * 0.1).astype(np.float32)
+    Bm = (rng.standard_normal((B, k, D)) * 0.1).astype(np.float32)
+    lam = np.sort(rng.uniform(0.0, 4.0 * k, (B, k)), axis=1); lam[:, 0] = 0.0
+    fresh = MatchEngine()
+    try:
+        fresh.fmap_solve(A, Bm, lam, lam + 0.5, np.ones(B), WD, WL)
+        got = fresh.workspace_bytes()
+    finally:
+        fresh.close()
+    assert got == 1 << 20 < ARENA_SMALL_ROUTE_BEFORE_THE_PLAN, got
+
