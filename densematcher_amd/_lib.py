@@ -103,6 +103,10 @@ SIGNATURES = {
     "dm_groupnorm_relu_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i]),
     "dm_conv3x3_f32": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _i]),
     "dm_agg_mix_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, C.c_uint, _p, _p, _i]),
+    "dm_vit_patch_rows_f16": (_i, [_p, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, C.POINTER(_d), C.POINTER(_d), _i, _p, _i]),
+    "dm_vit_layernorm_f16": (_i, [_p, _i, _i, _p, _i, _p, _p, _i, _p, _i]),
+    "dm_vit_linear_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _ll, _p, _i, _p, _p, _p, _i, _ll, _i, _i, _p, _i, _ll]),
+    "dm_vit_attention_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _ll, _p, _i, _ll]),
 }
 
 # the float64-basis forms (const double* Phi / mass): same argument lists

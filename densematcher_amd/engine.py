@@ -31,10 +31,11 @@ from ._engine_lift import _LiftOps
 from ._engine_mesh import _MeshOps
 from ._engine_network import _NetworkOps
 from ._engine_render import _RenderOps
+from ._engine_vit import _VitOps
 from ._operands import fits_abi, host_ptr, ptr as _ptr
 
 
-class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps, _JbuOps, _AggreOps, _EvalOps, _NetworkOps):
+class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps, _JbuOps, _AggreOps, _VitOps, _EvalOps, _NetworkOps):
     def __init__(self, device=None, lib_path=None):
         if not torch.cuda.is_available():
             raise RuntimeError("MatchEngine needs a ROCm GPU (gfx950); there is no CPU fallback")

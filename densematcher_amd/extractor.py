@@ -2,8 +2,19 @@
 densematcher.extractor of the reference, the part behind the 2D backbone (extractor.py:177-254): loading FeatUp's JBUStack from a
 released checkpoint, and the path from the backbone's low-resolution features to the per-view feature maps that lifting reads.  With
 load_aggre_net / features_from_backbone the path starts one stage earlier, at the raw outputs of the two frozen backbones (SD's s3, s4,
-s5 and DINO's tokens): the aggregation network (featurizers) runs here too.  The backbones themselves and the image preprocessing are
-outside this package.
+s5 and DINO's tokens): the aggregation network (featurizers) runs here too.  Of the two backbones the DINOv2 ViT is in this package
+(featurizers.dinov2, with a checkpoint the caller loads; its positional-embedding interpolation restates the reference's local copy of
+the rule and is not pinned against the hub model's own method); the SD model and the image-file preprocessing are outside it.
+
+A backbone= callable of MeshFeaturizer, images (views, 3, H, W) in [0, 1] -> (s3, s4, s5, dino), chains the caller's own SD call with
+this package's ViT:
+
+    vit = ViTExtractor("dinov2_vitb14", stride=14, model=load_dinov2(path, "dinov2_vitb14").to(device))     # featup.model_utils, featurizers.dinov2
+    def backbone(images):
+        sd = sd_model(images, raw=True)                                    # the caller's: SDDINO.py:46
+        return sd["s3"], sd["s4"], sd["s5"], dino_features(vit, images, num_patches)                    # featurizers.dino_features: SDDINO.py:49-51
+
+dino is a permuted view of the token buffer, which aggregate_features reads where it lies.
 """
 import os
 import re

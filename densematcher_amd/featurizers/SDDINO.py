@@ -1,8 +1,9 @@
 """
 densematcher.featurizers.SDDINO of the reference WITHOUT the backbones (SDDINO.py:35-90): what happens to the raw outputs of the frozen
 SD-1.5 and DINOv2 models on their way to features_lr.  There is no SDDINOFeaturizer class here -- the backbones are third-party models
-whose weights are not part of this package; a caller runs them and hands over s3, s4, s5 (the UNet's decoder features) and dino (the
-ViT's layer-11 tokens as a (B, C, P, P) view).
+whose weights are not part of this package; a caller runs SD and hands over s3, s4, s5 (the UNet's decoder features).  dino (the ViT's
+layer-11 tokens as a (B, C, P, P) view) comes from dino_features below: the DINOv2 encoder itself is featurizers.dinov2, with a
+checkpoint the caller loads.
 
 Routes of aggregate_features: 'torch' the reference's expressions (interpolate, cat, rotate, the network on torch), 'device' the HIP
 path (MatchEngine.agg_gather + MatchEngine.aggregate: the concatenated and rotated intermediates are never stored), 'auto' as
@@ -14,6 +15,25 @@ import torch.nn.functional as F
 from .. import _routes
 from .modules import projection_network as pn
 from .util import rotate
+
+
+def dino_features(extractor_vit, img_batch01, num_patches, route="auto"):
+    """SDDINO.py:49-51 (under the no_grad of SDDINO.py:44: the backbone is frozen): images (bs, 3, H, W) in [0, 1] -> resized to
+    14 num_patches and normalised (extractor_vit.mean / std), the tokens of block 11 without the cls token, as (bs, D, P, P): a
+    permuted view of the token buffer (the reference's reshape copies it), which aggregate_features reads where it lies.
+    extractor_vit: a featup.model_utils.extractor_dino.ViTExtractor.  route: as DinoVisionTransformer.tokens; on the device route the
+    resize and the normalisation happen while the patch rows are written."""
+    P = int(num_patches)
+    with torch.no_grad():
+        model = extractor_vit.model
+        if hasattr(model, "tokens_from_images"):
+            desc = model.tokens_from_images(img_batch01, P, extractor_vit.mean, extractor_vit.std, layer=11, route=route)[:, 1:]
+        else:                                                # another model under the hub's interface: the torch expressions only
+            _routes.check(route, _routes.TORCH)
+            if route == "device":
+                raise ValueError("dino_features route='device': the model is not a featurizers.dinov2.DinoVisionTransformer")
+            desc = extractor_vit.extract_descriptors(extractor_vit.resize_and_normalize(img_batch01, P * 14), layer=11, facet="token", route="torch")[:, 0]
+    return desc.permute(0, 2, 1).unflatten(2, (P, P))
 
 
 def gather_features(s3, s4, s5, dino, num_patches=None):

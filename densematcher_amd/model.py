@@ -3,13 +3,13 @@ densematcher.model of the reference: MeshFeaturizer, the module that turns a sim
 2D feature maps into normalised per-vertex descriptors (reference model.py:14-173).  extractor_3d and reconstructor are built as the
 reference builds them, so `model.extractor_3d.load_state_dict(...)` of the notebook loads with strict=True.
 
-The 2D backbone is outside this package: forward takes the per-view feature maps as fts=
+The SD half of the 2D backbone is outside this package: forward takes the per-view feature maps as fts=
 together with the cameras they were rendered with -- or, with an upsampler= (featup.upsamplers.JBUStack, extractor.load_upsampler),
 the backbone's low-resolution features fts_lr= and the images= they came from, which it upsamples 16x on the way into lifting; with
 an aggre_net= as well (featurizers.AggregationNetwork, extractor.load_aggre_net), the raw outputs of the two frozen backbones raw=
 (s3, s4, s5, dino); or a backbone= callable, images (views, 3, H, W) -> (s3, s4, s5, dino), for the views of mesh_raw that render.py
-renders here.  From there on -- back-projection (projection.get_features_per_vertex),
-positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
+renders here (extractor's module docstring shows one that chains the caller's SD model with this package's DINOv2 encoder,
+featurizers.dino_features).  From there on -- back-projection (projection.get_features_per_vertex), positional encoding, heat kernel signatures, DiffusionNet, the row normalisation -- everything runs here, on the device with
 route="device" (or "auto", see projection.AUTO_DEVICE and diffusion_net.layers.AUTO_DEVICE).
 """
 import numpy as np

@@ -933,6 +933,47 @@ int dm_agg_mix_f32(dm_ctx* ctx, int L, int B, int npix, int C, int G, const floa
                    const float* rstds, const float* gammas, const float* betas, unsigned identity_mask, const float* mix, float* out,
                    int ldo);
 
+/* ---- DINOv2 ViT encoder (inference) --------------------------------------------------------
+ * The frozen ViT behind the reference's `dino` tokens (featup/model_utils/extractor_dino.py through densematcher/featurizers/
+ * SDDINO.py:27, 49-51): patch embedding, pre-norm blocks with LayerScale, exact GELU.  fp16 operands on v_mfma_f32_32x32x16_f16 with fp32
+ * accumulation; the residual stream and the LayerNorm input stay fp32.  Every product is a fixed-order sum over ascending chunks of
+ * the contraction index, never split along it, no atomics: an image has the same bits alone and in any batch.  fp16 operands that a
+ * kernel reads with 16-byte loads (A, W, qkv, the attention output) are 16-byte aligned with leading dimensions and block strides that
+ * are multiples of 8 halves; everything else needs its natural alignment only.
+ *   dm_vit_patch_rows_f16
+ *     img (n, 3, S, S) fp16 | fp32 through ELEMENT strides (image, channel, row, col) -> out (n P P, Kp) fp16 rows with leading
+ *     dimension ldo: row i P P + py P + px, column k = 196 c + 14 dy + dx (Conv2d's flattening) holds (v - mean[c]) / std[c] in fp32
+ *     (mean, std: three HOST doubles each, rounded to fp32), rounded once to fp16, v the image resized to (14 P, 14 P) at
+ *     (14 py + dy, 14 px + dx): F.interpolate(bilinear, align_corners=False) with the coordinate and weight convention of
+ *     dm_agg_gather_f32, the pixel itself when S = 14 P.  Columns 588 .. Kp - 1 are zeros; Kp a multiple of 64.
+ *   dm_vit_layernorm_f16
+ *     x (M, D) fp32 -> out (M, D) fp16 (out_dtype DM_F16) or fp32: per row the fp64 sum, then the fp64 sum of squared deviations from
+ *     the fp64 mean (a lane's elements ascending, 64 partial sums through a fixed tree), biased variance, eps 1e-6;
+ *     out = fmaf((float)((x - mean) rstd), gamma, beta), rounded once more for an fp16 output.
+ *   dm_vit_linear_f16
+ *     out[b] = resid[b] + scale * act(A[b] W^T + bias) for B blocks of Mb rows: A (Mb, K) fp16 rows lda, blocks strideA apart; W (N, K)
+ *     fp16 as nn.Linear stores it; bias, scale (N) fp32 and resid (Mb, N) fp32 rows ldr, blocks strideR apart (0 broadcasts one
+ *     block), all three nullable; act 0 none, 1 erf-GELU 0.5 v (1 + erff(v / sqrt 2)); out fp32 | fp16, rows ldo, blocks strideO
+ *     apart.  Order: the fp32 accumulation, + bias, act, * scale, + resid, each rounded on its own.  out may alias resid.  Any Mb
+ *     and N; K a multiple of 64 (the granule).  No operand is read past a row's width.
+ *   dm_vit_attention_f16
+ *     qkv (n, T, 3 D) fp16, D = 64 heads, row t of image i at qkv + i stride_q + t ldq: q | k | v, heads adjacent within each.
+ *     out (n, T, D) fp16: softmax(q k^T / 8) v per (image, head).  Keys in ascending tiles of 32; q scaled by 0.125 in fp16; running
+ *     maximum and sum in fp32 (the sum of the unrounded weights), the weights rounded to fp16 for the second product, the output
+ *     rescaled at every tile and divided by the sum at the end.  Keys at positions >= T weigh exactly nothing.
+ * DM_EINVAL, checked on the host before any launch: a size that is not positive, a null operand, a leading dimension below its width,
+ * K not on the granule, a head dimension other than 64, a misaligned 16-byte operand, output blocks that overlap. */
+int dm_vit_patch_rows_f16(dm_ctx* ctx, int n, int S, int P, int src_dtype, const void* img, long long s_img, long long s_chan,
+                          long long s_row, long long s_col, const double* mean /*host*/, const double* std /*host*/, int Kp, void* out,
+                          int ldo);
+int dm_vit_layernorm_f16(dm_ctx* ctx, int M, int D, const float* x, int ldx, const float* gamma, const float* beta, int out_dtype,
+                         void* out, int ldo);
+int dm_vit_linear_f16(dm_ctx* ctx, int B, int Mb, int N, int K, const void* A, int lda, long long strideA, const void* W, int ldw,
+                      const float* bias /*nullable*/, const float* scale /*nullable*/, const float* resid /*nullable*/, int ldr,
+                      long long strideR, int act, int out_dtype, void* out, int ldo, long long strideO);
+int dm_vit_attention_f16(dm_ctx* ctx, int n, int T, int heads, int head_dim, const void* qkv, int ldq, long long stride_q, void* out,
+                         int ldo, long long stride_o);
+
 #ifdef __cplusplus
 }
 #endif
