@@ -38,6 +38,7 @@ SIGNATURES = {
     "dm_fmap_solve": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _d, _d, _p, _p]),
     "dm_fmap_fit": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _d, _d, _p, _p]),
     "dm_fmap_energy_grad": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
+    "dm_fmap_energy_plan": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _i, C.POINTER(C.c_int32)]),
     "dm_lbfgs_state_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm_lbfgs_init": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "dm_lbfgs_advance": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _d, _d, _i, _i, _i]),

@@ -661,50 +661,95 @@ extern "C" size_t dm_fmap_fit_keep_bytes(int B, int k1, int k2) {
     return ((size_t)B * (k1 + k2) * k1 + (size_t)B * (k1 + k2)) * 8;
 }
 
-// dm_fmap_energy_grad with that block (null: none), written by this evaluation or, keep_valid, read from an earlier one of the fit
-int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1, const float* Phi2,
-                             int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1, const double* lam2,
-                             const double* ops1, const double* ops2, int n_ops, const double* weights, const double* C, double* energy,
-                             double* grad, double* keep, bool keep_valid) {
-    if (!ctx) return DM_EINVAL;
-    DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && k1 > 0 && k2 > 0 && D > 0, "sizes must be positive");
-    DM_REQUIRE(ctx, A && Bm && lam1 && lam2 && weights && C && energy && grad, "null pointer");
-    double w[W_COUNT];
-    for (int q = 0; q < W_COUNT; ++q) {
-        w[q] = weights[q];
-        DM_REQUIRE(ctx, w[q] >= 0.0, "weights must be >= 0");
-    }
-    const mterm_weights mw{w[W_P2P], w[W_STOCH], w[W_ENT], w[W_RANGE01], w[W_SUMTO1]};
-    const bool m_terms = mw.p2p > 0 || mw.stoch > 0 || mw.ent > 0 || mw.range01 > 0 || mw.sumto1 > 0;
-    const bool dcomm = w[W_DCOMM] > 0.0 && n_ops > 0;
-    const bool shape = w[W_AREA] > 0.0 || w[W_CONFORMAL] > 0.0;
-    DM_REQUIRE(ctx, !m_terms || (Phi1 && Phi2 && mass1 && ld1 >= k1 && ld2 >= k2), "the indicator terms need Phi1, Phi2, mass1");
-    DM_REQUIRE(ctx, !(w[W_DCOMM] > 0.0) || (ops1 && ops2 && n_ops > 0), "w_dcomm > 0 needs the descriptor operators (dm_fmap_descr_ops)");
+// ---- the plan: every choice an evaluation makes from its sizes, its weights and the device's CU count, in one place -------------
+// (dm_fmap_energy_grad_keep launches from it; dm_fmap_energy_plan shows it to the caller.)  The indicator fields are 0 when no
+// indicator term is weighted.
+struct energy_plan {
+    int rg, ncs, cchunk, ngroups;          // pass 1: rows per workgroup; both passes: column splits, columns per split; row groups
+    int stats_route;                       // 0 none, 1 em_stats_linear_kernel, 2 em_stats_kernel + m_finish_stats_kernel
+    int cp_inline, e2_inline;              // maps up to 32 x 32: C P inside combine_kernel, E2 inside em_stats_linear_kernel
+    int nt2;                               // em_deriv_kernel<NT2>: 1, 2, 4 for k1 <= 64, 128, 256
+    int kc_m, nsplit_m, nsplit_d;          // split-K of Gm = Phi2^T Y (chunk, splits) and of the commutativity back product (0: no such term)
+    int m_terms;
+};
+static int energy_plan_make(dm_ctx* ctx, int n_cu, int B, int N1, int N2, int k1, int k2, const double* weights, int n_ops, energy_plan* pl) {
+    DM_REQUIRE(ctx, B > 0 && N1 > 0 && N2 > 0 && k1 > 0 && k2 > 0, "sizes must be positive");
+    DM_REQUIRE(ctx, weights, "null pointer");
+    for (int q = 0; q < W_COUNT; ++q) DM_REQUIRE(ctx, weights[q] >= 0.0, "weights must be >= 0");
+    const double* w = weights;
+    const bool m_terms = w[W_P2P] > 0 || w[W_STOCH] > 0 || w[W_ENT] > 0 || w[W_RANGE01] > 0 || w[W_SUMTO1] > 0;
+    DM_REQUIRE(ctx, !(w[W_DCOMM] > 0.0) || n_ops > 0, "w_dcomm > 0 needs the descriptor operators (dm_fmap_descr_ops)");
     DM_REQUIRE(ctx, !(w[W_DCOMM] > 0.0) || (long long)B * n_ops <= 65535, "too many (pair, descriptor) slots for one launch: split the batch");
     DM_REQUIRE(ctx, B <= 65535, "batch too large for one launch");
-    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-
-    const size_t bKK = (size_t)B * k2 * k1 * 8;
     DM_REQUIRE(ctx, !m_terms || k1 <= 256, "the indicator terms need k1 <= 256");
+    memset(pl, 0, sizeof(*pl));
+    pl->m_terms = m_terms;
+    pl->cp_inline = k1 <= 32 && k2 <= 32;                  // (by the map's size only)
+    pl->nsplit_d = (w[W_DCOMM] > 0.0 && n_ops > 0) ? dm_cdiv(n_ops * k2, 512) : 0;
+    if (!m_terms) return DM_OK;
     // Work decomposition of the two indicator passes: a workgroup sweeps `rg` rows x one column split.  A batch fills the chip
     // with whole-row sweeps (rg = 512, no splits); a single pair (the reference's use: one pair per call) would leave 252 of the
     // 256 CUs idle that way, so the row groups shrink to one 64-row block and the columns are split until ~1024 workgroups exist
     // (two per CU hide the other's log / divide chains; measured on the notebook fit, workgroups x column tiles each: 256 x 4
     // 56.7 + 30.6 us for the two passes, 512 x 2 46.0 + 21.6, 1024 x 1 50.6 + 21.1 with twice the partials to add up).
     int rg = EM_RG, ncs = 1;
-    {
-        const int ncu2 = 4 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-        while (rg > EM_T && (long long)B * dm_cdiv(N2, rg) < ncu2) rg >>= 1;
-        const int max_split = dm_cdiv(N1, 2 * EM_T) > 0 ? dm_cdiv(N1, 2 * EM_T) : 1;        // at least two column tiles per workgroup
-        while (ncs < max_split && (long long)B * dm_cdiv(N2, EM_T) * ncs < ncu2) ncs <<= 1;
-    }
-    const int cchunk = pad_to(dm_cdiv(N1, ncs), EM_T);
-    const int ngroups = dm_cdiv(N2, rg);
+    const int ncu2 = 4 * (n_cu > 0 ? n_cu : 256);
+    while (rg > EM_T && (long long)B * dm_cdiv(N2, rg) < ncu2) rg >>= 1;
+    const int max_split = dm_cdiv(N1, 2 * EM_T) > 0 ? dm_cdiv(N1, 2 * EM_T) : 1;        // at least two column tiles per workgroup
+    while (ncs < max_split && (long long)B * dm_cdiv(N2, EM_T) * ncs < ncu2) ncs <<= 1;
+    pl->rg = rg; pl->ncs = ncs;
+    pl->cchunk = pad_to(dm_cdiv(N1, ncs), EM_T);
+    pl->ngroups = dm_cdiv(N2, rg);
+    const bool stats = w[W_STOCH] > 0 || w[W_SUMTO1] > 0;
+    // (row and column SUMS are linear in the indicator: em_stats_linear_kernel; sums of squares, or a k2 wider than its 256
+    //  threads, take the tile pass)
+    pl->stats_route = !stats ? 0 : (!(w[W_STOCH] > 0) && k2 <= 256) ? 1 : 2;
+    // (maps up to 32 x 32 whose statistics come from em_stats_linear_kernel: that kernel writes E2 as well)
+    pl->e2_inline = pl->stats_route == 1 && k1 <= 32 && k2 <= 32;
+    const int nt2 = dm_cdiv(dm_cdiv(k1, 16), 4);
+    pl->nt2 = nt2 <= 1 ? 1 : nt2 <= 2 ? 2 : 4;
     // split-K chunk of Gm = Phi2^T Y: by the map's size only (a pair's sums must not depend on the batch it is in); a map of one
     // 64 x 64 tile has nothing else to fill the chip with, so its chunks are short (one pair, N2 = 2048: 4 -> 16 workgroups)
-    const int kc_m = (k1 <= TN_T && k2 <= TN_T) ? 128 : 512;
-    const int nsplit_m = dm_cdiv(N2, kc_m);
-    const int nsplit_d = dcomm ? dm_cdiv(n_ops * k2, 512) : 0;
+    pl->kc_m = (k1 <= TN_T && k2 <= TN_T) ? 128 : 512;
+    pl->nsplit_m = dm_cdiv(N2, pl->kc_m);
+    return DM_OK;
+}
+extern "C" int dm_fmap_energy_plan(const dm_ctx* ctx, int n_cu, int B, int N1, int N2, int k1, int k2, const double* weights, int n_ops,
+                                   int32_t out[12]) {
+    if (!out) return DM_EINVAL;
+    energy_plan pl;
+    int rc = energy_plan_make(const_cast<dm_ctx*>(ctx), ctx ? ctx->n_cu : n_cu, B, N1, N2, k1, k2, weights, n_ops, &pl);   // (writes the error text only)
+    if (rc) return rc;
+    const int v[12] = {pl.rg, pl.ncs, pl.cchunk, pl.ngroups, pl.stats_route, pl.cp_inline, pl.e2_inline, pl.nt2, pl.kc_m, pl.nsplit_m,
+                       pl.nsplit_d, pl.m_terms};
+    for (int q = 0; q < 12; ++q) out[q] = v[q];
+    return DM_OK;
+}
+
+// dm_fmap_energy_grad with that block (null: none), written by this evaluation or, keep_valid, read from an earlier one of the fit
+int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int D, const float* Phi1, int ld1, const float* Phi2,
+                             int ld2, const float* mass1, const float* A, const float* Bm, const double* lam1, const double* lam2,
+                             const double* ops1, const double* ops2, int n_ops, const double* weights, const double* C, double* energy,
+                             double* grad, double* keep, bool keep_valid) {
+    if (!ctx) return DM_EINVAL;
+    DM_REQUIRE(ctx, D > 0, "sizes must be positive");
+    DM_REQUIRE(ctx, A && Bm && lam1 && lam2 && weights && C && energy && grad, "null pointer");
+    energy_plan pl;
+    int rc = energy_plan_make(ctx, ctx->n_cu, B, N1, N2, k1, k2, weights, n_ops, &pl);
+    if (rc) return rc;
+    double w[W_COUNT];
+    for (int q = 0; q < W_COUNT; ++q) w[q] = weights[q];
+    const mterm_weights mw{w[W_P2P], w[W_STOCH], w[W_ENT], w[W_RANGE01], w[W_SUMTO1]};
+    const bool m_terms = pl.m_terms;
+    const bool dcomm = pl.nsplit_d > 0;
+    const bool shape = w[W_AREA] > 0.0 || w[W_CONFORMAL] > 0.0;
+    DM_REQUIRE(ctx, !m_terms || (Phi1 && Phi2 && mass1 && ld1 >= k1 && ld2 >= k2), "the indicator terms need Phi1, Phi2, mass1");
+    DM_REQUIRE(ctx, !(w[W_DCOMM] > 0.0) || (ops1 && ops2), "w_dcomm > 0 needs the descriptor operators (dm_fmap_descr_ops)");
+    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+
+    const size_t bKK = (size_t)B * k2 * k1 * 8;
+    const int rg = pl.rg, ncs = pl.ncs, cchunk = pl.cchunk, ngroups = pl.ngroups;       // (energy_plan_make)
+    const int kc_m = pl.kc_m, nsplit_m = pl.nsplit_m, nsplit_d = pl.nsplit_d;
     size_t need = dm_align_up((size_t)B * (k1 + k2) * k1 * 8) + 4 * dm_align_up(bKK) + 4 * dm_align_up((size_t)B * 8) + 65536;
     if (m_terms)      // O(N k): the mapped indicator is never stored (em_stats_kernel / em_deriv_kernel)
         need += dm_align_up((size_t)B * N2 * k1 * 8) + dm_align_up((size_t)ncs * B * N2 * k1 * 8) + 2 * dm_align_up((size_t)ncs * B * N2 * 8) +
@@ -712,7 +757,7 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
                 dm_align_up((size_t)B * ncs * dm_cdiv(N2, EM_T) * 8) + dm_align_up((size_t)nsplit_m * bKK) + 2 * dm_align_up((size_t)B * (k1 + k2) * 8);
     if (dcomm) need += dm_align_up((size_t)B * n_ops * k2 * k1 * 8) + dm_align_up((size_t)nsplit_d * bKK);
     if (shape) need += dm_align_up((size_t)B * 2 * k1 * k1 * 8) + dm_align_up(bKK) + dm_align_up((size_t)B * 8) + 4096;
-    int rc = dm_ws_reserve(ctx, need);
+    rc = dm_ws_reserve(ctx, need);
     if (rc) return rc;
     double* PQ = keep ? keep : (double*)dm_ws_take(ctx, (size_t)B * (k1 + k2) * k1 * 8);
     const bool reuse = keep && keep_valid;                 // P, Q (and p, s2 behind them) are what an earlier evaluation of the fit wrote
@@ -737,7 +782,7 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
         KRowsF64 ca{C, (long long)k2 * k1, k1, k2, k1, 0};
         KRowsF64 pb{PQ, (long long)(k1 + k2) * k1, k1, k1, k1, 1};          // (C P)_ij = sum_k C_ik P_kj
         OutNT ocp{CP, (long long)k2 * k1, k1};
-        const bool cp_inline = k1 <= 32 && k2 <= 32;      // (by the map's size only)
+        const bool cp_inline = pl.cp_inline;
         if (!cp_inline)
             DM_LAUNCH(ctx, "energy_cp_nt_f64", (gemm_nt_f64<KRowsF64, KRowsF64, OutNT>), dim3(dm_cdiv(k2, NT_T) * dm_cdiv(k1, NT_T), 1, B),
                       dim3(256), 0, ca, pb, ocp, k2, k1, k1);
@@ -753,7 +798,6 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
     memset(&cm, 0, sizeof(cm));
     if (m_terms) {
         const int nrb = dm_cdiv(N2, EM_T);
-        const bool stats = mw.stoch > 0 || mw.sumto1 > 0;
         double* E2 = (double*)dm_ws_take(ctx, (size_t)B * N2 * k1 * 8);            // Phi2 C
         double* Yv = (double*)dm_ws_take(ctx, (size_t)ncs * B * N2 * k1 * 8);      // Y = D' Phi1, one partial per column split
         double* rs = (double*)dm_ws_take(ctx, (size_t)ncs * B * N2 * 8);
@@ -768,8 +812,7 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
         double* part = (double*)dm_ws_take(ctx, (size_t)nsplit_m * bKK);
         if (!E2 || !Yv || !rs || !rsq || !cs || !csq || !pcs || !pcsq || !stat || !pe || !part)
             return dm_fail(ctx, DM_ENOMEM, "energy: workspace not reserved");
-        // (maps up to 32 x 32 whose statistics come from em_stats_linear_kernel: that kernel writes E2 as well)
-        const bool e2_inline = stats && !(mw.stoch > 0) && k1 <= 32 && k2 <= 32;
+        const bool e2_inline = pl.e2_inline;
         if (!e2_inline) {   // E2 = Phi2 C   (the left factor of the mapped indicator, convert.py:144)
             KRowsF32 opa{Phi2, (long long)N2 * ld2, ld2, N2, k2};
             KRowsF64 opb{C, (long long)k2 * k1, k1, k1, k2, 1};
@@ -784,7 +827,7 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
         ep.rg = rg; ep.ncs = ncs; ep.cchunk = cchunk; ep.Bn = B;
         ep.rs = rs; ep.rsq = rsq; ep.pcs = pcs; ep.pcsq = pcsq; ep.ngroups = ngroups; ep.cs = cs; ep.csq = csq; ep.stat = stat; ep.nstat = nstat;
         ep.w = mw; ep.Y = Yv; ep.pe = pe;
-        if (stats && !(mw.stoch > 0) && k2 <= 256) {
+        if (pl.stats_route == 1) {
             double* pv = keep ? keep + (size_t)B * (k1 + k2) * k1 : (double*)dm_ws_take(ctx, (size_t)B * k1 * 8);
             double* s2 = keep ? pv + (size_t)B * k1 : (double*)dm_ws_take(ctx, (size_t)B * k2 * 8);
             if (!pv || !s2) return dm_fail(ctx, DM_ENOMEM, "energy: workspace not reserved");
@@ -795,7 +838,7 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
             }
             DM_LAUNCH(ctx, "energy_stats_linear", em_stats_linear_kernel, dim3(nstat, B), dim3(256), 0, E2, Phi1, ld1, mass1, N1, N2, k1, k2,
                       C, (const double*)pv, (const double*)s2, rs, rsq, cs, csq, stat, e2_inline ? Phi2 : (const float*)nullptr, ld2);
-        } else if (stats) {
+        } else if (pl.stats_route == 2) {
             const size_t lds1 = ((size_t)EM_T * EM_LDA + 2 * EM_RG + 2 * 2 * 2 * 64) * 8 + (size_t)EM_T * ep.ldp * 4;
             rc = dm_grant_lds(ctx, (const void*)em_stats_kernel, lds1);
             if (rc) return rc;
@@ -805,14 +848,13 @@ int dm_fmap_energy_grad_keep(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2,
         }
         {
             const size_t lds2 = ((size_t)EM_T * EM_LDA + EM_T * EM_LDD) * 8 + (size_t)EM_T * ep.ldp * 4;
-            const int nt2 = dm_cdiv(dm_cdiv(k1, 16), 4);
 #define EM_DERIV(NT2_)                                                                                                  \
             {                                                                                                          \
                 rc = dm_grant_lds(ctx, (const void*)em_deriv_kernel<NT2_>, lds2);                                      \
                 if (rc) return rc;                                                                                     \
                 DM_LAUNCH(ctx, "energy_deriv_tiles", em_deriv_kernel<NT2_>, dim3(nrb, ncs, B), dim3(256), lds2, ep);   \
             }
-            if (nt2 <= 1) EM_DERIV(1) else if (nt2 <= 2) EM_DERIV(2) else EM_DERIV(4)
+            if (pl.nt2 == 1) EM_DERIV(1) else if (pl.nt2 == 2) EM_DERIV(2) else EM_DERIV(4)
 #undef EM_DERIV
         }
         if (ncs > 1) {

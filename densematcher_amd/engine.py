@@ -353,12 +353,26 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
 
     def energy_grad(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
         """Energy (B,) and gradient (B,k2,k1) of the functional-map objective for the weights in `weights` (dict with keys
-        of WEIGHT_ORDER; reference energy_func_std / grad_energy_std, base_functions.py:480-763)."""
+        of WEIGHT_ORDER; reference energy_func_std / grad_energy_std, base_functions.py:480-763).
+        A pair's bits: identical whenever the plan (energy_plan: the row groups and column splits follow the batch size and the CU
+        count) is the same, e.g. in repeated calls and in batches of 1, 2, 3; in a batch whose plan differs the sums of the indicator
+        terms are added in another order and the result is equal to rounding (1e-17 of max |grad| measured), not bit for bit."""
         o = self._fit_operands(Cm, A, Bm, lam1, lam2, weights, Phi1, Phi2, a1, ops1, ops2)
         energy = torch.empty((o.B,), dtype=torch.float64, device=self.device)
         grad = torch.empty((o.B, o.k2, o.k1), dtype=torch.float64, device=self.device)
         self._chk(self.lib.dm_fmap_energy_grad(self.ctx, *o.head, *o.ops, o.w, _ptr(o.C), _ptr(energy), _ptr(grad)))
         return energy, grad
+
+    ENERGY_PLAN_FIELDS = ("rg", "ncs", "cchunk", "ngroups", "stats_route", "cp_inline", "e2_inline", "nt2", "kc_m", "nsplit_m", "nsplit_d", "m_terms")
+
+    def energy_plan(self, B, N1, N2, k1, k2, weights, n_ops=0):
+        """The work decomposition energy_grad takes for these sizes and weights on this engine's device, as a dict of
+        ENERGY_PLAN_FIELDS (include/densematch.h: dm_fmap_energy_plan); nothing is launched.  ValueError for sizes or weights
+        energy_grad refuses."""
+        out = (C.c_int32 * 12)()
+        w = self._weight_array(weights)
+        self._chk(self.lib.dm_fmap_energy_plan(self.ctx, 0, int(B), int(N1), int(N2), int(k1), int(k2), C.cast(w, C.c_void_p), int(n_ops), out))
+        return dict(zip(self.ENERGY_PLAN_FIELDS, (int(v) for v in out)))
 
     def _fit_operands(self, Cm, A, Bm, lam1, lam2, weights, Phi1=None, Phi2=None, a1=None, ops1=None, ops2=None):
         """The operand list of a fit, once, for dm_fmap_energy_grad, dm_fmap_fit_steps and dm_fmap_fit_fused: the tensors on the device
@@ -512,9 +526,12 @@ class MatchEngine(_MeshOps, _GeodesicOps, _DiffusionNetOps, _LiftOps, _RenderOps
                     precision="auto"):
         """FunctionalMapping.fit for any of the implemented energy terms, a whole batch at once (reference: L-BFGS-B through
         scipy.optimize.minimize, one pair per call, functional.py:477).  Every pair runs its OWN limited-memory BFGS iteration --
-        history, step length, stopping test -- so a pair's result does not depend on the batch it is in; the optimiser state
+        history, step length, stopping test -- so no pair's iteration is steered by another's; the optimiser state
         lives on the device (dm_lbfgs_*), energy and gradient of all pairs come from one dm_fmap_energy_grad call per
         evaluation, and the host reads the status words every `check_every` evaluations.
+        A pair's result is bit-identical whenever the evaluations run under the same plan (energy_plan; batches of 1, 2, 3 at the
+        tested sizes), and always on the fused route (maps up to 32 x 32, fit_fused_ok); between batches whose plans differ the
+        evaluations agree to rounding (energy_grad), so the fitted maps agree to the stopping rule's accuracy, not bit for bit.
         lbfgs_options: maxcor, ftol, gtol, maxfun, maxls with SciPy's names; default = SciPy's defaults (LBFGS_REFERENCE).
         driver="scipy" (single pair only): the same evaluations driven by scipy.optimize.minimize on the host, as the reference.
         x0 (B,k2,k1): start, its first column is the pinned one.  Returns (C (B,k2,k1) numpy, result) with result.x, .fun (B),

@@ -225,6 +225,20 @@ int dm_fmap_energy_grad(dm_ctx* ctx, int B, int N1, int N2, int k1, int k2, int 
                         const float* A, const float* Bm, const double* lam1, const double* lam2,
                         const double* ops1 /*nullable*/, const double* ops2 /*nullable*/, int n_ops,
                         const double* weights /*host, 10*/, const double* C, double* energy, double* grad);
+/* What dm_fmap_energy_grad will do for these sizes: host only, launches nothing. ctx may be NULL, then n_cu is used (<= 0: 256).
+ * out[12]: rg, ncs, cchunk, ngroups, stats_route, cp_inline, e2_inline, nt2, kc_m, nsplit_m, nsplit_d, m_terms
+ *   rg          rows of the mapped indicator per workgroup of the statistics tile pass (64, 128, 256, 512)
+ *   ncs, cchunk column splits of both tile passes and the columns of one split (trailing splits may be empty); ngroups = ceil(N2 / rg)
+ *   stats_route 0: no row / column statistics; 1: from the basis sums (w_sumto1 without w_stochastic, k2 <= 256); 2: the tile pass
+ *   cp_inline, e2_inline   maps up to 32 x 32: C A A^T / Phi2 C are formed inside another kernel instead of by a product launch
+ *   nt2         16-column tiles of the derivative pass per wave: 1, 2, 4 for k1 <= 64, 128, 256
+ *   kc_m, nsplit_m   split-K chunk and splits of Phi2^T Y; nsplit_d: splits of the commutativity back product (0: no such term)
+ *   m_terms     1 when an indicator term is weighted; otherwise the indicator fields (all but cp_inline, nsplit_d) are 0
+ * rg, ncs, cchunk and ngroups depend on the batch size and the CU count, the others on the map's sizes and the weights alone.  Two
+ * evaluations of a pair under the same plan give the same bits.  Returns what dm_fmap_energy_grad returns for sizes and weights
+ * it refuses (DM_EINVAL). */
+int dm_fmap_energy_plan(const dm_ctx* ctx, int n_cu, int B, int N1, int N2, int k1, int k2, const double* weights /*host, 10*/, int n_ops,
+                        int32_t out[12]);
 
 /* ---- batched L-BFGS on the device --------------------------------------------------------------------------------
  * The optimiser FunctionalMapping.fit runs for the non-quadratic terms: replaces scipy.optimize.minimize(method = "L-BFGS-B")
