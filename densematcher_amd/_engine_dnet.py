@@ -1,12 +1,25 @@
 """
-MatchEngine, DiffusionNet: the operators of a batch of meshes and the fp32 forward pass.
+MatchEngine, DiffusionNet: the operators of a batch of meshes and the forward pass, fp32 or -- for a halved module -- fp16 operands.
 """
 import ctypes as C
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._operands import pad_stack, ptr as _ptr
+
+_HALF_OR_SINGLE = (torch.float16, torch.float32)
+
+
+def _flag(t):
+    return _lib.DM_F16 if t.dtype == torch.float16 else _lib.DM_F32
+
+
+def _kept(t):
+    """the dtype in which a floating-point operand goes to the fp16 kernels: its own when it is float16 or float32, else float32"""
+    dtype = t.dtype if isinstance(t, torch.Tensor) else torch.as_tensor(t).dtype
+    return dtype if dtype in _HALF_OR_SINGLE else torch.float32
 
 
 class _DiffusionNetOps:
@@ -135,12 +148,12 @@ class _DiffusionNetOps:
             raise ValueError(f"n_verts: expected {Bn} counts, got {tuple(nv.shape)}")
         return nv
 
-    def _dnet_out(self, out, Bn, N, C, name):
+    def _dnet_out(self, out, Bn, N, C, name, dtype=torch.float32):
         if out is None:
-            return torch.empty((Bn, N, C), dtype=torch.float32, device=self.device), C
-        if out.dtype != torch.float32 or out.device != self.device or tuple(out.shape) != (Bn, N, C):
-            raise ValueError(f"{name}: out must be a float32 ({Bn}, {N}, {C}) tensor on {self.device}")
-        o, ld = self._strided(out, torch.float32, name)
+            return torch.empty((Bn, N, C), dtype=dtype, device=self.device), C
+        if out.dtype != dtype or out.device != self.device or tuple(out.shape) != (Bn, N, C):
+            raise ValueError(f"{name}: out must be a {str(dtype)[6:]} ({Bn}, {N}, {C}) tensor on {self.device}")
+        o, ld = self._strided(out, dtype, name)
         if o is not out:
             raise ValueError(f"{name}: out must have adjacent elements in a row and evenly spaced rows")
         return out, ld
@@ -221,7 +234,90 @@ class _DiffusionNetOps:
                                                 _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
         return out
 
-    def diffusion_net_forward(self, weights, packed, x):
+    # ------------------------------------------------------------- DiffusionNet forward, fp16 operands (dm_dnet_*_f16)
+    def dnet_linear_f16(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None, out_dtype=torch.float32):
+        """dnet_linear on fp16 operands (dm_dnet_linear_f16): every source float16 or float32 in its own dtype (float32 elements are
+        rounded as they are staged), weight (C_out, sum w_s) float16 read where it lies, bias float16 or float32, resid float32;
+        fp32 accumulation, + bias, act, + resid; out float32 or float16 (out_dtype, or the dtype of out)."""
+        srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError("dnet_linear_f16: one to three sources")
+        flat = srcs[0].dim() == 2
+        if flat:
+            srcs = [s.unsqueeze(0) for s in srcs]
+            resid = None if resid is None else resid.unsqueeze(0)
+        mats = [self._strided(s, _kept(s), "src") for s in srcs]
+        Bn, N = mats[0][0].shape[:2]
+        if any(m.shape[:2] != (Bn, N) for m, _ in mats):
+            raise ValueError("dnet_linear_f16: the sources differ in their leading dimensions")
+        W, ldw = self._strided(weight, torch.float16, "weight")
+        if W.dim() != 2 or W.shape[1] != sum(m.shape[2] for m, _ in mats):
+            raise ValueError(f"dnet_linear_f16: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
+        C_out = W.shape[0]
+        bias = None if bias is None else self._dev(bias, _kept(bias), "bias")
+        if bias is not None and bias.shape != (C_out,):
+            raise ValueError("dnet_linear_f16: bias must be (C_out,)")
+        R, ldr = (None, 0) if resid is None else self._strided(resid, torch.float32, "resid")
+        if R is not None and tuple(R.shape) != (Bn, N, C_out):
+            raise ValueError("dnet_linear_f16: resid must have the shape of the output")
+        nv = self._dnet_counts(n_verts, Bn)
+        out_dtype = out_dtype if out is None else out.dtype
+        if out_dtype not in _HALF_OR_SINGLE:
+            raise ValueError("dnet_linear_f16: the output is float32 or float16")
+        out, ldo = self._dnet_out(out, Bn, N, C_out, "dnet_linear_f16", out_dtype)
+        a = [(m, m.shape[2], ld, _flag(m)) for m, ld in mats] + [(None, 0, 0, _lib.DM_F32)] * (3 - len(mats))
+        self._chk(self.lib.dm_dnet_linear_f16(self.ctx, Bn, N, C_out, len(mats), _ptr(a[0][0]), *a[0][1:], _ptr(a[1][0]), *a[1][1:], _ptr(a[2][0]), *a[2][1:],
+                                              _ptr(W), ldw, _ptr(bias), _lib.DM_F32 if bias is None else _flag(bias), _ptr(R), ldr, 1 if relu else 0,
+                                              _ptr(nv), _flag(out), _ptr(out), ldo))
+        return out[0] if flat else out
+
+    def dnet_diffuse_f16(self, x, evecs_h, mevecs_h, e1, e2, evals, times, n_verts=None, out=None):
+        """evecs (exp(-evals max(times, 1e-8)) * (evecs^T (mass * x))) on fp16 operands (dm_dnet_diffuse_f16): x (B,N,C) float32;
+        evecs_h, mevecs_h (B,N,K) float16 and e1, e2 (B) int32 as PackedOperators.half_operands() returns them; evals (B,K) float32;
+        times (C) float16 or float32.  Returns float32."""
+        X, ldx = self._strided(x, torch.float32, "x")
+        E, lde = self._strided(evecs_h, torch.float16, "evecs_h")
+        M, ldm = self._strided(mevecs_h, torch.float16, "mevecs_h")
+        Bn, N, Cw = X.shape
+        K = E.shape[2]
+        evals = self._dev(evals, torch.float32, "evals")
+        times = self._dev(times, _kept(times), "times")
+        e1, e2 = self._dev(e1, torch.int32, "e1"), self._dev(e2, torch.int32, "e2")
+        if (tuple(E.shape[:2]) != (Bn, N) or M.shape != E.shape or tuple(evals.shape) != (Bn, K) or tuple(times.shape) != (Cw,)
+                or tuple(e1.shape) != (Bn,) or tuple(e2.shape) != (Bn,)):
+            raise ValueError("dnet_diffuse_f16: x (B,N,C), evecs_h / mevecs_h (B,N,K), e1 / e2 (B), evals (B,K), times (C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_diffuse_f16")
+        self._chk(self.lib.dm_dnet_diffuse_f16(self.ctx, Bn, N, K, Cw, _ptr(X), ldx, _ptr(E), lde, _ptr(M), ldm, _ptr(e1), _ptr(e2), _ptr(evals),
+                                               _ptr(times), _flag(times), _ptr(nv), _ptr(out), ldo))
+        return out
+
+    def dnet_gradient_features_f16(self, x, row_len, cols, gx, gy, A_re, A_im=None, n_verts=None, out=None):
+        """dnet_gradient_features with float16 A_re / A_im (dm_dnet_gradfeat_f16): the gradients come from the float32 rows and the
+        float32 x in float32 and are rounded only as operands of the products with the matrices.  Returns float32."""
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        row_len = self._dev(row_len, torch.int32, "row_len")
+        cols = self._dev(cols, torch.int32, "cols")
+        gx = self._dev(gx, torch.float32, "gx")
+        gy = self._dev(gy, torch.float32, "gy")
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError("dnet_gradient_features_f16: row_len (B,N), cols / gx / gy (B,N,nnz)")
+        Are, lda = self._strided(A_re, torch.float16, "A_re")
+        Aim = None
+        if A_im is not None:
+            Aim, lda2 = self._strided(A_im, torch.float16, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError("dnet_gradient_features_f16: A_re / A_im must be (C, C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_f16")
+        self._chk(self.lib.dm_dnet_gradfeat_f16(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
+                                                _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
+        return out
+
+    def diffusion_net_forward(self, weights, packed, x, out_dtype=None):
         """A whole DiffusionNet (inference) on a padded batch: first_lin, per block diffuse -> gradient features -> the MLP (its first
         layer reads (x, x_diffuse, x_grad) as three sources, its last adds the skip), last_lin.
         weights  {"first": (W, b), "last": (W, b), "blocks": [{"times": t, "A_re": A or None, "A_im": A or None, "mlp": [(W, b), ...]}]},
@@ -229,29 +325,44 @@ class _DiffusionNetOps:
         packed   fp32 padded operators with the attributes mass (B,N), evals (B,K), evecs (B,N,K), row_len, cols, gx, gy, n_verts_dev
                  ((B) int32 or None when no mesh is padded) -- diffusion_net.layers.PackedOperators
         x        (B, N, C_in), or up to three tensors read as concatenated along the channels.
-        Returns (B, N, C_out); rows behind a mesh's count are zero.  Intermediates live in buffers that the blocks share."""
+        Returns (B, N, C_out); rows behind a mesh's count are zero.  Intermediates live in buffers that the blocks share.
+        The dtype of weights["first"][0] picks the kernels: float32 the dm_dnet_*_f32 family, float16 (a module after .half()) the
+        dm_dnet_*_f16 family on packed.half_operands(), with float32 intermediates.  out_dtype: float32, or for float16 weights
+        float16 (their default, the reference's return dtype: the float32 result rounded once)."""
         nv = packed.n_verts_dev
         W0, b0 = weights["first"]
-        cur = self.dnet_linear(x, W0, b0, n_verts=nv)
+        half = W0.dtype == torch.float16
+        if out_dtype is None:
+            out_dtype = torch.float16 if half else torch.float32
+        if out_dtype != torch.float32 and not (half and out_dtype == torch.float16):
+            raise ValueError("diffusion_net_forward: out_dtype is float32, or float16 with float16 weights")
+        if half:
+            evecs_h, mevecs_h, e1, e2 = packed.half_operands()
+            linear, gradfeat = self.dnet_linear_f16, self.dnet_gradient_features_f16
+            diffuse = lambda x, times, out: self.dnet_diffuse_f16(x, evecs_h, mevecs_h, e1, e2, packed.evals, times, n_verts=nv, out=out)
+        else:
+            linear, gradfeat = self.dnet_linear, self.dnet_gradient_features
+            diffuse = lambda x, times, out: self.dnet_diffuse(x, packed.mass, packed.evals, packed.evecs, times, n_verts=nv, out=out)
+        cur = linear(x, W0, b0, n_verts=nv)
         Bn, N, Cw = cur.shape
         buf = lambda c=Cw: torch.empty((Bn, N, c), dtype=torch.float32, device=self.device)
         nxt, xd, xg, hidden = buf(), buf(), None, {}
         for blk in weights["blocks"]:
-            self.dnet_diffuse(cur, packed.mass, packed.evals, packed.evecs, blk["times"], n_verts=nv, out=xd)
+            diffuse(cur, blk["times"], xd)
             src = [cur, xd]
             if blk.get("A_re") is not None:
                 xg = buf() if xg is None else xg
-                self.dnet_gradient_features(xd, packed.row_len, packed.cols, packed.gx, packed.gy, blk["A_re"], blk.get("A_im"), n_verts=nv, out=xg)
+                gradfeat(xd, packed.row_len, packed.cols, packed.gx, packed.gy, blk["A_re"], blk.get("A_im"), n_verts=nv, out=xg)
                 src.append(xg)
             mlp = blk["mlp"]
             for i, (W, b) in enumerate(mlp):
                 if i + 1 == len(mlp):
-                    self.dnet_linear(src, W, b, resid=cur, n_verts=nv, out=nxt)
+                    linear(src, W, b, resid=cur, n_verts=nv, out=nxt)
                 else:
                     key = (i % 2, W.shape[0])
                     if key not in hidden:
                         hidden[key] = buf(W.shape[0])
-                    src = [self.dnet_linear(src, W, b, relu=True, n_verts=nv, out=hidden[key])]
+                    src = [linear(src, W, b, relu=True, n_verts=nv, out=hidden[key])]
             cur, nxt = nxt, cur
         W1, b1 = weights["last"]
-        return self.dnet_linear(cur, W1, b1, n_verts=nv)
+        return linear(cur, W1, b1, n_verts=nv, out_dtype=out_dtype) if half else linear(cur, W1, b1, n_verts=nv)

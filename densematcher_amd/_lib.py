@@ -68,6 +68,9 @@ SIGNATURES = {
     "dm_dnet_linear_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i]),
     "dm_dnet_diffuse_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i]),
     "dm_dnet_gradfeat_f32": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i]),
+    "dm_dnet_linear_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i]),
+    "dm_dnet_diffuse_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i]),
+    "dm_dnet_gradfeat_f16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i]),
     "dm_heat_geodesic_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm_heat_geodesic_factor": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dm_heat_geodesic_solve": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),

@@ -4,9 +4,12 @@ state_dict keys (a released checkpoint loads with strict=True), and two routes t
 
   torch    the reference's expressions on PyTorch, on any device and dtype, with autograd: spectral and implicit_dense diffusion,
            torch.mm(gradX, .) per mesh, the two concatenations, dropout in training mode.
-  device   inference in fp32 HIP (MatchEngine.diffusion_net_forward: dm_dnet_linear_f32, dm_dnet_diffuse_f32, dm_dnet_gradfeat_f32).
-           It needs a GPU, float32 input and parameters, eval mode or dropout=False, diffusion_method="spectral", and no autograd
-           graph to record (torch.no_grad(), or no input and no parameter that requires grad); otherwise RuntimeError names the condition.
+  device   inference in HIP (MatchEngine.diffusion_net_forward).  A float32 module with float32 input runs dm_dnet_linear_f32,
+           dm_dnet_diffuse_f32, dm_dnet_gradfeat_f32; a module after .half() (every parameter float16; each input float16 or float32)
+           runs dm_dnet_linear_f16, dm_dnet_diffuse_f16, dm_dnet_gradfeat_f16 -- fp16 matrix operands, fp32 accumulation and an fp32
+           residual stream -- and returns float16, as the reference's half route does.
+           It needs a GPU, eval mode or dropout=False, diffusion_method="spectral", and no autograd graph to record (torch.no_grad(),
+           or no input and no parameter that requires grad); otherwise RuntimeError names the condition.
 route="auto" takes the device route where those conditions hold and tools/dnet_forward_time.py measured it faster (AUTO_DEVICE below),
 else torch.  The outputs_at / last_activation tail is the same torch code behind both.
 
@@ -23,8 +26,9 @@ from .. import _routes
 from .geometry import from_basis, to_basis
 
 # where tools/dnet_forward_time.py measured the device route faster than the torch route on an MI355X (README.md):
-# "single" = one mesh per call, "batch" = several meshes in one call
-AUTO_DEVICE = {"single": True, "batch": True}
+# "single" = one mesh per call, "batch" = several meshes in one call; "..._half": the same for a module after .half(), against the torch
+# route of that module under torch.autocast("cuda")
+AUTO_DEVICE = {"single": True, "batch": True, "single_half": True, "batch_half": True}
 
 TIME_FLOOR = 1e-8
 
@@ -43,13 +47,30 @@ class PackedOperators:
             setattr(self, key, tensors[key])
         N = self.mass.shape[1]
         self.n_verts_dev = None if min(self.n_verts) == N else torch.tensor(self.n_verts, dtype=torch.int32, device=self.mass.device)
+        self._half = None               # half_operands(), built on first use
 
     @property
     def device(self):
         return self.mass.device
 
     def to(self, device):
+        """the pack on another device; its half_operands() are built there anew"""
         return PackedOperators(self.n_verts, **{key: getattr(self, key).to(device) for key in self.FIELDS})
+
+    def half_operands(self):
+        """(evecs_h, mevecs_h, e1, e2), the matrix operands of the fp16 diffusion (dm_dnet_diffuse_f16), built once on the pack's device:
+        evecs_h = fp16(2^e1[b] evecs) and mevecs_h = fp16(2^e2[b] mass * evecs), (B,N,K) float16, each rounded once from the exact
+        float64 value; e1, e2 (B) int32, per mesh the exponents that put the operand's largest magnitude in [2^14, 2^15) (0 for an
+        operand of zeros).  Rows behind a mesh's count hold zeros."""
+        if self._half is None:
+            real = torch.arange(self.mass.shape[1], device=self.device)[None, :] < torch.tensor(self.n_verts, device=self.device)[:, None]
+            evecs = torch.where(real[:, :, None], self.evecs.to(torch.float64), 0.0)
+            mevecs = self.mass.to(torch.float64)[:, :, None] * evecs                   # 24 x 24 bits: exact
+            e1, e2 = _window_exponent(evecs), _window_exponent(mevecs)
+            two_to = lambda e: ((e.to(torch.int64) + 1023) << 52).view(torch.float64)   # 2^e from its bit pattern: exact
+            up = lambda a, e: _round_to_half(a * two_to(e)[:, None, None])
+            self._half = (up(evecs, e1), up(mevecs, e2), e1, e2)
+        return self._half
 
     def dense_grad(self, b, which="gx"):
         """(n, n) dense gradX (which="gx") or gradY ("gy") of mesh b, from its ELL rows"""
@@ -60,6 +81,23 @@ class PackedOperators:
         rows = torch.arange(n, device=cols.device)[:, None].expand_as(cols)
         out[rows[keep], cols[keep]] = vals[keep]
         return out
+
+
+def _window_exponent(a):
+    """per mesh of a (B,N,K) float64 batch the integer e with 2^e max |a[b]| in [2^14, 2^15), 0 where a[b] is all zeros: (B) int32"""
+    top = a.abs().amax(dim=(1, 2))
+    _, x = torch.frexp(top)                                                             # top = f 2^x, f in [0.5, 1)
+    return torch.where(top > 0, 15 - x, torch.zeros_like(x)).to(torch.int32)
+
+
+def _round_to_half(p):
+    """float64 -> float16 with ONE rounding to nearest even: first to float32 with round-to-odd (the last bit records that the value was
+    inexact, so the second rounding sees on which side of a tie it lies), then the usual conversion"""
+    f = p.to(torch.float32)
+    d, u = f.to(torch.float64), f.view(torch.int32)
+    odd = torch.where(d.abs() < p.abs(), u + 1, u - 1)
+    u = torch.where((d != p) & ((u & 1) == 0), odd, u)
+    return u.view(torch.float32).to(torch.float16)
 
 
 def _ell_from_coo(gradX, gradY, n, device):
@@ -295,11 +333,24 @@ class DiffusionNet(nn.Module):
         if self.training and self.dropout:
             return "the module must be in eval mode or built with dropout=False"
         params = list(self.parameters())
-        if any(t.dtype != torch.float32 for t in list(xs) + params):
-            return "the input and the parameters must be float32"
+        why = self._dtype_obstacle(xs)
+        if why is not None:
+            return why
         if any(not p.is_cuda for p in params):
             return "the parameters must be on the GPU"
         return _routes.grad_obstacle(list(xs) + params + [t for t in extra if isinstance(t, torch.Tensor)])
+
+    def _dtype_obstacle(self, xs):
+        """None for a float32 module with float32 inputs or a float16 module with float16 / float32 inputs, else what is wrong"""
+        kinds = {p.dtype for p in self.parameters()}
+        if kinds == {torch.float32}:
+            return None if all(x.dtype == torch.float32 for x in xs) else "the input and the parameters must be float32"
+        if kinds == {torch.float16}:
+            return None if all(x.dtype in (torch.float16, torch.float32) for x in xs) else "with float16 parameters every input must be float16 or float32"
+        return "the parameters must be all float32 or all float16, not " + ", ".join(sorted(str(k)[6:] for k in kinds))
+
+    def is_half(self):
+        return self.first_lin.weight.dtype == torch.float16
 
     def _tail(self, x, mass, edges, faces):
         if self.outputs_at == "vertices":
@@ -348,7 +399,7 @@ class DiffusionNet(nn.Module):
             xs = [x.unsqueeze(0) for x in xs]
             mass, L, evals, evecs, gradX, gradY, edges, faces = (up(t) for t in (mass, L, evals, evecs, gradX, gradY, edges, faces))
         picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs)),
-                                    AUTO_DEVICE["batch" if xs[0].shape[0] > 1 else "single"], refusal=RuntimeError)
+                                    AUTO_DEVICE[("batch" if xs[0].shape[0] > 1 else "single") + ("_half" if self.is_half() else "")], refusal=RuntimeError)
         self.last_route = picked
         if picked == "torch":
             if mass is None or (self.diffusion_method == "spectral" and (evals is None or evecs is None)):
@@ -386,7 +437,7 @@ class DiffusionNet(nn.Module):
         Bn, N = len(per), packed.mass.shape[1]
         xs = []
         for s in range(len(per[0])):
-            buf = torch.zeros((Bn, N, per[0][s].shape[-1]), dtype=torch.float32, device=per[0][s].device)
+            buf = torch.zeros((Bn, N, per[0][s].shape[-1]), dtype=per[0][s].dtype, device=per[0][s].device)
             for b, p in enumerate(per):
                 buf[b, :p[s].shape[0]] = p[s]
             xs.append(buf)

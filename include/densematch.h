@@ -545,6 +545,46 @@ int dm_dnet_gradfeat_f32(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_
                          const float* x, int ldx, const float* A_re, const float* A_im /*nullable*/, int lda, const int32_t* n_verts /*nullable*/,
                          float* out, int ldo);
 
+/* ---- DiffusionNet forward pass (inference), fp16 operands ------------------------------
+ * The same network for a module after .half(), as the reference's driver runs it (model.half() under torch.autocast): the three
+ * entries above with fp16 matrix operands.  Every product is exact fp16 x fp16 accumulated in fp32 on v_mfma_f32_32x32x16_f16 over
+ * ascending chunks of 16 of the contraction index, never split, no atomics; the residual stream and everything one kernel hands to
+ * the next stay fp32.  An output element depends on its own row and column of the operands only: a mesh has the same bits alone and
+ * in any batch, whatever tile shape the launch picked.  A value is rounded to fp16 (to nearest even) exactly once, at the places
+ * named below and nowhere else; a magnitude beyond 65504 becomes infinite there, as in the reference's half route.  fp16 operands
+ * need 2-byte alignment only (nn.Linear's (C_out, 835) weight is read where it lies); dtype flags are DM_F16 | DM_F32.
+ *   dm_dnet_linear_f16    the expression of dm_dnet_linear_f32.  Each source is fp32 or fp16 (dtype_s); an fp32 source element is
+ *                         ROUNDED as it is staged.  W (C_out, sum w) fp16.  bias fp16 or fp32 (bias_dtype), widened exactly; resid fp32.
+ *                         Order: the accumulation, + bias, act, + resid, in fp32.  out fp32, or fp16 (out_dtype): that value ROUNDED
+ *                         once more.  Tiles: 128 x 128 outputs per workgroup when ceil(C_out / 128) ceil(N / 128) B >= 256 (one for
+ *                         every CU), 64 x 64 below; the bits do not depend on it.
+ *   dm_dnet_diffuse_f16   evecs_h = fp16(2^e1[b] evecs), mevecs_h = fp16(2^e2[b] mass * evecs) (B,N,K), prepared once per mesh with
+ *                         per-mesh integer exponents that put each operand's largest magnitude in [2^14, 2^15)
+ *                         (PackedOperators.half_operands): the vertex masses, at the bottom of fp16's normal range, are never rounded
+ *                         on their own.  x fp32, ROUNDED as it is staged.  acc = mevecs_h^T x over ascending vertices in fp32;
+ *                         coef[k,c] = exp(-evals[k] max(times[c], 1e-8f)) in float64, rounded once to fp32 (times fp16 or fp32, widened
+ *                         exactly); d = coef * acc * 2^(14 - e1 - e2), the exact float64 product ROUNDED once to fp16 -- the spectrum at
+ *                         the scale of the product back, so that evecs -> s evecs, mass -> mass / s^2 (s a power of two) moves no bit;
+ *                         out = 2^-14 (evecs_h d) over ascending k, fp32.  One workgroup per (mesh, 32 channels) keeps d in LDS: K <= 1024.
+ *   dm_dnet_gradfeat_f16  gX = G_x x, gY = G_y x in fp32 from the fp32 ELL rows and the fp32 x, as dm_dnet_gradfeat_f32 (the reference
+ *                         keeps this product in fp32 under autocast).  gX, gY are ROUNDED only as operands of the products with A_re /
+ *                         A_im (fp16, A_im nullable); out = tanhf(gX * B_re + gY * B_im) with the unrounded gX, gY; out fp32.
+ *                         Where the rounded gradients of 32 rows fit in LDS for every channel (C <= 768) and ceil(N / 32) B >= 256, a
+ *                         workgroup owns 32 rows and gathers them once for all columns; else 64 x 64 tiles gather per column tile,
+ *                         as the fp32 kernel.  The bits do not depend on it.
+ * n_verts, the leading dimensions and DM_EINVAL as for the fp32 entries; also an unknown dtype flag or an operand not aligned to its
+ * element. */
+int dm_dnet_linear_f16(dm_ctx* ctx, int B, int N, int C_out, int n_src, const void* src0, int w0, int ld0, int dtype0, const void* src1, int w1,
+                       int ld1, int dtype1, const void* src2, int w2, int ld2, int dtype2, const void* W, int ldw, const void* bias /*nullable*/,
+                       int bias_dtype, const float* resid /*nullable*/, int ldr, int act, const int32_t* n_verts /*nullable*/, int out_dtype,
+                       void* out, int ldo);
+int dm_dnet_diffuse_f16(dm_ctx* ctx, int B, int N, int K, int C, const float* x, int ldx, const void* evecs_h, int lde, const void* mevecs_h,
+                        int ldm, const int32_t* e1, const int32_t* e2, const float* evals, const void* times, int times_dtype,
+                        const int32_t* n_verts /*nullable*/, float* out, int ldo);
+int dm_dnet_gradfeat_f16(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx, const float* gy,
+                         const float* x, int ldx, const void* A_re, const void* A_im /*nullable*/, int lda, const int32_t* n_verts /*nullable*/,
+                         float* out, int ldo);
+
 /* ---- heat-method geodesic distances ------------------------------------------------
  * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
  * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors
