@@ -1,5 +1,6 @@
 """
-MatchEngine, DiffusionNet: the operators of a batch of meshes and the forward pass, fp32 or -- for a halved module -- fp16 operands.
+MatchEngine, DiffusionNet: the operators of a batch of meshes, the forward pass, fp32 or -- for a halved module -- fp16 operands, and
+the backward pass of the fp32 kernels.
 """
 import ctypes as C
 
@@ -233,6 +234,145 @@ class _DiffusionNetOps:
         self._chk(self.lib.dm_dnet_gradfeat_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
                                                 _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
         return out
+
+    # ------------------------------------------------------------- DiffusionNet backward (dm_dnet_*_bwd_f32)
+    def _dnet_ws(self, nbytes):
+        return torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=self.device)
+
+    def dnet_linear_backward(self, grad_out, srcs, weight, y=None, n_verts=None, need_src=True, need_weight=True, need_bias=True, out=None):
+        """The gradients of dnet_linear (dm_dnet_linear_bwd_data_f32, dm_dnet_linear_bwd_weight_f32).  grad_out (B, N, C_out); srcs the
+        forward's sources; weight (C_out, sum w_s); y: the saved output of a relu=True call made WITHOUT resid (its mask y > 0 is
+        applied to grad_out), None for relu=False.  The gradient of resid is grad_out itself.  need_src: one flag, or one per source;
+        out: a list with a (B, N, w_s) tensor or None per source.  Only the weight and bias gradients read the sources: without
+        them a source may be given as its width (an int).
+        Returns (list of source gradients or None each, grad_weight or None, grad_bias or None)."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        flat = G.dim() == 2
+        if flat:
+            G = G.unsqueeze(0)
+        Bn, N, C_out = G.shape
+        srcs = [srcs] if isinstance(srcs, (torch.Tensor, int)) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError("dnet_linear_backward: one to three sources")
+        widths = [int(s) if isinstance(s, int) else int(s.shape[-1]) for s in srcs]
+        need_src = [bool(need_src)] * len(srcs) if isinstance(need_src, bool) else [bool(f) for f in need_src]
+        if len(need_src) != len(srcs):
+            raise ValueError("dnet_linear_backward: need_src has one flag per source")
+        W, ldw = (None, 0)
+        if any(need_src):
+            if weight is None:
+                raise ValueError("dnet_linear_backward: the gradient of a source reads the weight")
+            W, ldw = self._strided(weight, torch.float32, "weight")
+            if W.dim() != 2 or tuple(W.shape) != (C_out, sum(widths)):
+                raise ValueError(f"dnet_linear_backward: weight {tuple(W.shape)} does not match grad_out ({C_out}) and the summed source widths {sum(widths)}")
+        Y, ldy = (None, 0)
+        if y is not None:
+            Y, ldy = self._strided(y.unsqueeze(0) if flat else y, torch.float32, "y")
+            if tuple(Y.shape) != (Bn, N, C_out):
+                raise ValueError("dnet_linear_backward: y must have the shape of grad_out")
+        nv = self._dnet_counts(n_verts, Bn)
+        act = 0 if Y is None else 1
+        d_src = [None] * len(srcs)
+        if any(need_src):
+            outs = [None] * len(srcs) if out is None else list(out)
+            a = []
+            for s, (w, need) in enumerate(zip(widths, need_src)):
+                if need:
+                    d_src[s], ld = self._dnet_out(None if outs[s] is None else (outs[s].unsqueeze(0) if flat else outs[s]), Bn, N, w,
+                                                  "dnet_linear_backward")
+                    a.append((d_src[s], w, ld))
+                else:
+                    a.append((None, w, w))
+            a += [(None, 0, 0)] * (3 - len(a))
+            self._chk(self.lib.dm_dnet_linear_bwd_data_f32(self.ctx, Bn, N, C_out, len(srcs), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(W), ldw, _ptr(nv),
+                                                           _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2]))
+        dW = db = None
+        if need_weight or need_bias:
+            if any(isinstance(s, int) for s in srcs):
+                raise ValueError("dnet_linear_backward: the weight and bias gradients read the sources")
+            mats = [self._strided(s.unsqueeze(0) if flat else s, torch.float32, "src") for s in srcs]
+            if any(tuple(m.shape[:2]) != (Bn, N) for m, _ in mats):
+                raise ValueError("dnet_linear_backward: the sources differ from grad_out in their leading dimensions")
+            a = [(m, m.shape[2], ld) for m, ld in mats] + [(None, 0, 0)] * (3 - len(mats))
+            dW = torch.empty((C_out, sum(widths)), dtype=torch.float32, device=self.device) if need_weight else None
+            db = torch.empty((C_out,), dtype=torch.float32, device=self.device) if need_bias else None
+            ws = self._dnet_ws(self.lib.dm_dnet_linear_bwd_bytes(Bn, C_out, sum(widths)))
+            self._chk(self.lib.dm_dnet_linear_bwd_weight_f32(self.ctx, Bn, N, C_out, len(mats), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(a[0][0]), a[0][1],
+                                                             a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2], _ptr(nv), _ptr(ws),
+                                                             _ptr(dW), sum(widths), _ptr(db)))
+        if flat:
+            d_src = [None if d is None else d[0] for d in d_src]
+        return d_src, dW, db
+
+    def dnet_diffuse_backward(self, grad_out, x, mass, evals, evecs, times, n_verts=None, need_x=True, need_times=True, out=None):
+        """The gradients of dnet_diffuse (dm_dnet_diffuse_bwd_f32) with respect to x and to the clamped times: grad_out, x (B,N,C) (x
+        may be None with need_times=False), the operators as in dnet_diffuse.  Returns (grad_x or None, grad_times or None)."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        E, lde = self._strided(evecs, torch.float32, "evecs")
+        Bn, N, Cw = G.shape
+        K = E.shape[2]
+        X, ldx = (None, 0)
+        if need_times:
+            X, ldx = self._strided(x, torch.float32, "x")
+            if tuple(X.shape) != (Bn, N, Cw):
+                raise ValueError("dnet_diffuse_backward: x must have the shape of grad_out")
+        mass = self._dev(mass, torch.float32, "mass")
+        evals = self._dev(evals, torch.float32, "evals")
+        times = self._dev(times, torch.float32, "times")
+        if tuple(E.shape[:2]) != (Bn, N) or tuple(mass.shape) != (Bn, N) or tuple(evals.shape) != (Bn, K) or tuple(times.shape) != (Cw,):
+            raise ValueError("dnet_diffuse_backward: grad_out (B,N,C), mass (B,N), evals (B,K), evecs (B,N,K), times (C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_diffuse_backward") if need_x else (None, 0)
+        dt = torch.empty((Cw,), dtype=torch.float32, device=self.device) if need_times else None
+        ws = self._dnet_ws(self.lib.dm_dnet_diffuse_bwd_bytes(Bn, K, Cw))
+        self._chk(self.lib.dm_dnet_diffuse_bwd_f32(self.ctx, Bn, N, K, Cw, _ptr(G), ldg, _ptr(X), ldx, _ptr(mass), _ptr(evals), _ptr(E), lde, _ptr(times),
+                                                   _ptr(nv), _ptr(ws), _ptr(dx), lddx, _ptr(dt)))
+        return dx, dt
+
+    def dnet_gradient_features_backward(self, grad_out, x, row_len, cols, gx, gy, rows_t, A_re, A_im=None, n_verts=None, need_x=True, need_A=True,
+                                        out=None):
+        """The gradients of dnet_gradient_features (dm_dnet_gradfeat_bwd_f32): grad_out and the saved x (B,N,C), the forward's rows,
+        rows_t = (row_len_t, cols_t, gx_t, gy_t), the rows of the transposed operators (PackedOperators.transposed_rows(); None with
+        need_x=False).  Returns (grad_x or None, grad_A_re or None, grad_A_im or None)."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        if tuple(G.shape) != (Bn, N, Cw):
+            raise ValueError("dnet_gradient_features_backward: grad_out must have the shape of x")
+        row_len = self._dev(row_len, torch.int32, "row_len")
+        cols = self._dev(cols, torch.int32, "cols")
+        gx = self._dev(gx, torch.float32, "gx")
+        gy = self._dev(gy, torch.float32, "gy")
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError("dnet_gradient_features_backward: row_len (B,N), cols / gx / gy (B,N,nnz)")
+        rl_t = cols_t = gx_t = gy_t = None
+        nnz_t = 0
+        if need_x:
+            if rows_t is None:
+                raise ValueError("dnet_gradient_features_backward: the gradient of x reads the transposed rows")
+            rl_t, cols_t = self._dev(rows_t[0], torch.int32, "row_len_t"), self._dev(rows_t[1], torch.int32, "cols_t")
+            gx_t, gy_t = self._dev(rows_t[2], torch.float32, "gx_t"), self._dev(rows_t[3], torch.float32, "gy_t")
+            if (cols_t.dim() != 3 or tuple(cols_t.shape[:2]) != (Bn, N) or gx_t.shape != cols_t.shape or gy_t.shape != cols_t.shape
+                    or tuple(rl_t.shape) != (Bn, N)):
+                raise ValueError("dnet_gradient_features_backward: row_len_t (B,N), cols_t / gx_t / gy_t (B,N,nnz_t)")
+            nnz_t = cols_t.shape[2]
+        Are, lda = self._strided(A_re, torch.float32, "A_re")
+        Aim = None
+        if A_im is not None:
+            Aim, lda2 = self._strided(A_im, torch.float32, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError("dnet_gradient_features_backward: A_re / A_im must be (C, C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_backward") if need_x else (None, 0)
+        dAre = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A else None
+        dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
+        ws = self._dnet_ws(self.lib.dm_dnet_gradfeat_bwd_bytes(Bn, N, Cw))
+        self._chk(self.lib.dm_dnet_gradfeat_bwd_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t),
+                                                    _ptr(cols_t), _ptr(gx_t), _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
+                                                    _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
+        return dx, dAre, dAim
 
     # ------------------------------------------------------------- DiffusionNet forward, fp16 operands (dm_dnet_*_f16)
     def dnet_linear_f16(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None, out_dtype=torch.float32):

@@ -68,6 +68,13 @@ SIGNATURES = {
     "dm_dnet_linear_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _i, _i, _p, _p, _i]),
     "dm_dnet_diffuse_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _i]),
     "dm_dnet_gradfeat_f32": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i]),
+    "dm_dnet_linear_bwd_data_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i]),
+    "dm_dnet_linear_bwd_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_linear_bwd_weight_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _i, _p]),
+    "dm_dnet_diffuse_bwd_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_diffuse_bwd_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p]),
+    "dm_dnet_gradfeat_bwd_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_gradfeat_bwd_f32": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i]),
     "dm_dnet_linear_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i]),
     "dm_dnet_diffuse_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i]),
     "dm_dnet_gradfeat_f16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i]),

@@ -10,19 +10,25 @@ state_dict keys (a released checkpoint loads with strict=True), and two routes t
            residual stream -- and returns float16, as the reference's half route does.
            It needs a GPU, eval mode or dropout=False, diffusion_method="spectral", and no autograd graph to record (torch.no_grad(),
            or no input and no parameter that requires grad); otherwise RuntimeError names the condition.
+           differentiable=True (with route="device", opt-in) records the autograd graph instead: a float32 module with float32 input
+           runs the same three fp32 kernels as torch.autograd.Functions whose backward is dm_dnet_linear_bwd_data_f32 /
+           dm_dnet_linear_bwd_weight_f32, dm_dnet_diffuse_bwd_f32, dm_dnet_gradfeat_bwd_f32 (diffusion_net/backward.py); dropout, the
+           tail and the loss stay torch operations, so training mode works.  It needs a GPU, diffusion_method="spectral", float32
+           parameters and inputs and k_eig <= 1024.
 route="auto" takes the device route where those conditions hold and tools/dnet_forward_time.py measured it faster (AUTO_DEVICE below),
-else torch.  The outputs_at / last_activation tail is the same torch code behind both.
+else torch; it never takes the differentiable device route (route="torch" and route="auto" ignore differentiable=).  The outputs_at / last_activation tail is the same torch code behind both.
 
 The device route reads the operators from a PackedOperators (pack_operators): fp32 padded batches of mass, evals, evecs and the ELL rows
 of gradX / gradY, built once per mesh set and passed as operators=; given the reference's tensors instead, forward packs them per call.
 DiffusionNet.forward_many runs a ragged list of meshes as one batched device call.
 
-Not built on the device: training / backward, implicit_dense, point clouds (their operators are not built either).
+Not built on the device: a backward for the fp16 kernels, implicit_dense, point clouds (their operators are not built either).
 """
 import torch
 import torch.nn as nn
 
 from .. import _routes
+from .backward import K_MAX, run as run_differentiable
 from .geometry import from_basis, to_basis
 
 # where tools/dnet_forward_time.py measured the device route faster than the torch route on an MI355X (README.md, DESIGN.md section 4):
@@ -48,6 +54,7 @@ class PackedOperators:
         N = self.mass.shape[1]
         self.n_verts_dev = None if min(self.n_verts) == N else torch.tensor(self.n_verts, dtype=torch.int32, device=self.mass.device)
         self._half = None               # half_operands(), built on first use
+        self._rows_t = None             # transposed_rows(), built on first use
 
     @property
     def device(self):
@@ -71,6 +78,36 @@ class PackedOperators:
             up = lambda a, e: _round_to_half(a * two_to(e)[:, None, None])
             self._half = (up(evecs, e1), up(mevecs, e2), e1, e2)
         return self._half
+
+    def transposed_rows(self):
+        """(row_len_t, cols_t, gx_t, gy_t), the ELL rows of gradX^T and gradY^T on their union pattern, built once on the pack's device
+        (the backward of the gradient features gathers over them): row_len_t (B,N) int32, cols_t (B,N,nnz_t) int32 ascending in a
+        row, gx_t, gy_t (B,N,nnz_t) float32, with the padding of the forward's rows (a row without entries, and every row behind
+        n_verts[b]: length 1 on its own column with value 0).  No symmetry of the pattern is assumed; entries of rows or columns
+        outside a mesh are dropped."""
+        if self._rows_t is None:
+            Bn, N, nnz = self.cols.shape
+            dev = self.device
+            nv = torch.tensor(self.n_verts, device=dev)[:, None, None]
+            cols = self.cols.long()
+            keep = ((torch.arange(nnz, device=dev)[None, None, :] < self.row_len[:, :, None]) & (torch.arange(N, device=dev)[None, :, None] < nv)
+                    & (cols >= 0) & (cols < nv))
+            b, i, _ = keep.nonzero(as_tuple=True)
+            j, vx, vy = cols[keep], self.gx[keep], self.gy[keep]
+            order = torch.argsort((b * N + j) * N + i, stable=True)          # by (mesh, transposed row, transposed column)
+            b, i, j, vx, vy = b[order], i[order], j[order], vx[order], vy[order]
+            row = b * N + j
+            count = torch.bincount(row, minlength=Bn * N)
+            slot = torch.arange(row.numel(), device=dev) - (torch.cumsum(count, 0) - count)[row]
+            nnz_t = max(int(count.max()) if row.numel() else 1, 1)
+            cols_t = torch.arange(N, dtype=torch.int32, device=dev)[None, :, None].repeat(Bn, 1, nnz_t)
+            gx_t = torch.zeros((Bn, N, nnz_t), dtype=torch.float32, device=dev)
+            gy_t = torch.zeros_like(gx_t)
+            cols_t.view(Bn * N, nnz_t)[row, slot] = i.to(torch.int32)
+            gx_t.view(Bn * N, nnz_t)[row, slot] = vx
+            gy_t.view(Bn * N, nnz_t)[row, slot] = vy
+            self._rows_t = (count.clamp(min=1).to(torch.int32).view(Bn, N), cols_t, gx_t, gy_t)
+        return self._rows_t
 
     def dense_grad(self, b, which="gx"):
         """(n, n) dense gradX (which="gx") or gradY ("gy") of mesh b, from its ELL rows"""
@@ -322,22 +359,27 @@ class DiffusionNet(nn.Module):
         self.last_route = None          # the route the last forward took ("torch" or "device")
 
     # ------------------------------------------------------------------ routes
-    def _device_obstacle(self, xs, extra=()):
-        """None when the device route can run for these inputs, else the condition that keeps it from running"""
+    def _device_obstacle(self, xs, extra=(), differentiable=False, k_eig=None):
+        """None when the device route can run for these inputs, else the condition that keeps it from running.  differentiable: the
+        route that records the autograd graph (training mode and tensors that require grad are no obstacles; float32 only)"""
         if not torch.cuda.is_available():
             return "it needs a ROCm GPU (gfx950)"
         if any(not x.is_cuda for x in xs):
             return "the input must be on the GPU"
         if self.diffusion_method != "spectral":
             return "diffusion_method must be 'spectral' (implicit_dense is not built on the device)"
-        if self.training and self.dropout:
+        if self.training and self.dropout and not differentiable:
             return "the module must be in eval mode or built with dropout=False"
         params = list(self.parameters())
+        if differentiable and any(t.dtype != torch.float32 for t in list(xs) + params):
+            return "the parameters and inputs must be float32 (the fp16 kernels have no backward)"
         why = self._dtype_obstacle(xs)
         if why is not None:
             return why
         if any(not p.is_cuda for p in params):
             return "the parameters must be on the GPU"
+        if differentiable:
+            return None if k_eig is None or k_eig <= K_MAX else "k_eig must be at most {} (the diffusion kernels' limit), not {}".format(K_MAX, k_eig)
         return _routes.grad_obstacle(list(xs) + params + [t for t in extra if isinstance(t, torch.Tensor)])
 
     def _dtype_obstacle(self, xs):
@@ -373,18 +415,22 @@ class DiffusionNet(nn.Module):
         return {"first": (self.first_lin.weight.data, self.first_lin.bias.data), "last": (self.last_lin.weight.data, self.last_lin.bias.data),
                 "blocks": [b.device_weights() for b in self.blocks]}
 
-    def _run_device(self, xs, packed):
+    def _run_device(self, xs, packed, differentiable=False):
         from ..engine import default_engine
         eng = default_engine(xs[0].device)
         if packed.device != eng.device:
             packed = packed.to(eng.device)
+        if differentiable:
+            return run_differentiable(self, eng, xs, packed)
         with torch.no_grad():
             return eng.diffusion_net_forward(self.device_weights(), packed, xs if len(xs) > 1 else xs[0])
 
-    def forward(self, x_in, mass=None, L=None, evals=None, evecs=None, gradX=None, gradY=None, edges=None, faces=None, *, route="auto", operators=None):
+    def forward(self, x_in, mass=None, L=None, evals=None, evecs=None, gradX=None, gradY=None, edges=None, faces=None, *, route="auto", operators=None,
+                differentiable=False):
         """x_in (N,C_in) or (B,N,C_in), or a tuple of up to three such tensors read as concatenated along the channels; mass (N) / (B,N),
         L, evals (K), evecs (N,K), gradX, gradY sparse (N,N) (or with the batch dimension), edges / faces for outputs_at.
-        operators: a PackedOperators of the B meshes (device route; mass may then be None).  Returns (N,C_out) or (B,N,C_out), or what
+        operators: a PackedOperators of the B meshes (device route; mass may then be None).  differentiable: with route="device", record
+        the autograd graph through the backward kernels (module docstring); ignored by route="torch" and route="auto".  Returns (N,C_out) or (B,N,C_out), or what
         outputs_at makes of it."""
         xs = list(x_in) if isinstance(x_in, (tuple, list)) else [x_in]
         if not 1 <= len(xs) <= 3:
@@ -398,7 +444,9 @@ class DiffusionNet(nn.Module):
             up = lambda t: None if t is None else t.unsqueeze(0)
             xs = [x.unsqueeze(0) for x in xs]
             mass, L, evals, evecs, gradX, gradY, edges, faces = (up(t) for t in (mass, L, evals, evecs, gradX, gradY, edges, faces))
-        picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs)),
+        differentiable = bool(differentiable) and route == "device"
+        k_eig = operators.evals.shape[-1] if operators is not None else (None if evals is None else evals.shape[-1])
+        picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs), differentiable, k_eig),
                                     AUTO_DEVICE[("batch" if xs[0].shape[0] > 1 else "single") + ("_half" if self.is_half() else "")], refusal=RuntimeError)
         self.last_route = picked
         if picked == "torch":
@@ -417,20 +465,20 @@ class DiffusionNet(nn.Module):
                                          for b in range(Bn)], device=xs[0].device)
             if len(packed.n_verts) != xs[0].shape[0] or packed.mass.shape[1] != xs[0].shape[1]:
                 raise ValueError("operators: packed for {} meshes of up to {} vertices, x_in is {}".format(len(packed.n_verts), packed.mass.shape[1], tuple(xs[0].shape)))
-            x = self._run_device(xs, packed)
+            x = self._run_device(xs, packed, differentiable)
             if mass is None:
                 mass = packed.mass
         x_out = self._tail(x, mass, edges, faces)
         return x_out.squeeze(0) if flat else x_out
 
-    def forward_many(self, x_list, packed, edges=None, faces=None):
+    def forward_many(self, x_list, packed, edges=None, faces=None, differentiable=False):
         """A ragged list of meshes as ONE batched device call: x_list[b] (n_b, C_in), or a tuple of up to three such tensors per mesh;
         packed: the PackedOperators of the same meshes.  Returns the list of outputs, each what forward() returns for its mesh alone
-        (edges / faces: lists, for outputs_at)."""
+        (edges / faces: lists, for outputs_at).  differentiable: as in forward."""
         per = [list(x) if isinstance(x, (tuple, list)) else [x] for x in x_list]
         if len(per) != len(packed.n_verts) or any(p[0].shape[0] != n for p, n in zip(per, packed.n_verts)):
             raise ValueError("forward_many: x_list does not match the packed meshes")
-        why = self._device_obstacle([x for p in per for x in p])
+        why = self._device_obstacle([x for p in per for x in p], (), bool(differentiable), packed.evals.shape[-1])
         if why is not None:
             raise RuntimeError("DiffusionNet.forward_many: " + why)
         self.last_route = "device"
@@ -443,7 +491,7 @@ class DiffusionNet(nn.Module):
             xs.append(buf)
         if sum(x.shape[-1] for x in xs) != self.C_in:
             raise ValueError("DiffusionNet was constructed with C_in={}, but x_list has last dim={}".format(self.C_in, sum(x.shape[-1] for x in xs)))
-        x = self._run_device(xs, packed)
+        x = self._run_device(xs, packed, bool(differentiable))
         mass = packed.mass.to(x.device)
         return [self._tail(x[b:b + 1, :n], mass[b:b + 1, :n], None if edges is None else edges[b].unsqueeze(0),
                            None if faces is None else faces[b].unsqueeze(0)).squeeze(0) for b, n in enumerate(packed.n_verts)]

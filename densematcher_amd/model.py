@@ -138,7 +138,7 @@ class MeshFeaturizer(nn.Module):
         return [o[5] for o in outs], [(o[1].R, o[1].T) for o in outs]
 
     def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto", fts_lr=None,
-                images=None, raw=None, backbone=None, image_size=None):
+                images=None, raw=None, backbone=None, image_size=None, differentiable=False):
         """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
         and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
         this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
@@ -148,6 +148,8 @@ class MeshFeaturizer(nn.Module):
         (images (views, 3, H, W) -> (s3, s4, s5, dino)): mesh_raw (verts_list / faces_list, optional .textures) is rendered with
         `cameras` (generated from num_views when None) at image_size (default: the extractor's size, else 512), the images go to the
         backbone and the result takes the raw= route with images=.
+        differentiable: passed to extractor_3d (DiffusionNet.forward): with route='device' the refiner records its autograd graph
+        through the backward kernels, so a training step stays on the device route.
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
         _routes.check(route, _routes.HOST)
         if fts is None and fts_lr is None and raw is None and backbone is not None:
@@ -169,11 +171,11 @@ class MeshFeaturizer(nn.Module):
                 raise ValueError("forward takes one mesh: a PackedOperators of several meshes goes to forward_many")
             packed = operators.to(self.device) if operators.device != self.device else operators
             sources = (lifted,) + self._neck(verts, packed.evals[0], packed.evecs[0, :verts.shape[0]])
-            raw = self.extractor_3d(sources, route=net_route, operators=packed)
+            raw = self.extractor_3d(sources, route=net_route, operators=packed, differentiable=differentiable)
         else:
             ops = [None if op is None else op.to(self.device) for op in operators]       # frames, mass, L, evals, evecs, gradX, gradY
             sources = (lifted,) + self._neck(verts, ops[3], ops[4])
-            raw = self.extractor_3d(sources, ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], route=net_route)
+            raw = self.extractor_3d(sources, ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], route=net_route, differentiable=differentiable)
         unit = self._normalize(raw)
         return (unit, raw, lifted) if return_mvfeatures else unit
 

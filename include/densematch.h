@@ -585,6 +585,66 @@ int dm_dnet_gradfeat_f16(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_
                          const float* x, int ldx, const void* A_re, const void* A_im /*nullable*/, int lda, const int32_t* n_verts /*nullable*/,
                          float* out, int ldo);
 
+/* ---- DiffusionNet backward pass (training) ---------------------------------------------
+ * The gradients of the three fp32 forward entries with respect to their activations and parameters (the operators of a mesh -- mass,
+ * evals, evecs, the gradient rows -- are constants).  Everything is fp32; every product is an fp32 fmaf chain on
+ * v_mfma_f32_32x32x2_f32 that starts at +0 and runs in ascending order of the contraction index; no atomics.  Operands beyond a mesh's
+ * rows, columns or ELL slots are staged as zeros.  Matrix operands are row-major with a leading dimension (batch stride N * ld); no
+ * pointer needs more than 4-byte alignment.  n_verts (device, nullable): rows i >= n_verts[b] are never read, and are written as zeros
+ * in every gradient of an activation.
+ * Order guarantees.
+ *   - A gradient with respect to an activation (B,N,.) depends on its own mesh only: the same bits alone and in any batch.
+ *   - A gradient with respect to a parameter contracts over the vertices: ONE chain per mesh and element over the mesh's vertices in
+ *     ascending order (into the workspace), then the meshes are added in ascending order, ((P_0 + P_1) + P_2) + ..  With B = 1 the
+ *     result is P_0.  Neither depends on the CU count or on a tile shape.
+ * Workspace: caller-owned device memory of at least the matching dm_dnet_*_bwd_bytes, 4-byte aligned; its contents afterwards are
+ * unspecified.  An output that is null is not computed.
+ *   dm_dnet_linear_bwd_data_f32    dZ = dY * [Y > 0] for act = 1 (Y: the saved output of the forward call WITHOUT its resid term;
+ *                         applied while a tile is staged, never stored), dZ = dY for act = 0 (Y not read).  With resid the forward
+ *                         adds it after the activation: its gradient is dY itself, no kernel.
+ *                         d_s[b,i,:] = dZ[b,i,:] W[:, off_s : off_s + w_s], the chain over o = 0 .. C_out-1; W is read where it lies.
+ *                         Every source has its own output and leading dimension; a null d_s skips that source.
+ *   dm_dnet_linear_bwd_weight_f32  P_b[o, off_s + k] = sum_i dZ[b,i,o] src_s[b,i,k] and P_b[o, K_tot] = sum_i dZ[b,i,o] (the chain
+ *                         fma(dZ, 1, s)), i ascending over the mesh; dW (C_out, K_tot), db (C_out) = the meshes added in ascending
+ *                         order.  Workspace dm_dnet_linear_bwd_bytes(B, C_out, K_tot): the partials (B, C_out, K_tot + 1).
+ *   dm_dnet_diffuse_bwd_f32        g = evecs^T dO, s = evecs^T (mass * x) (mass * x rounded to fp32 as in the forward), both over
+ *                         ascending vertices; coef as in the forward (float64 exp, rounded once).  H = fl(coef g);
+ *                         dx = fl(mass * (evecs H)), the chain over ascending k.  T = fl(fl(fl(evals coef) g) s);
+ *                         dtimes[c] = -((m_0 + m_1) + ..), m_b the running sum of T[b,k,c] over ascending k from +0.  The gradient
+ *                         is with respect to the clamped time (the caller clamps the parameter in place before the forward).  x is
+ *                         read for dtimes only.  Workspace dm_dnet_diffuse_bwd_bytes(B, K, C): H and T (B,K,C) in global memory, no
+ *                         spectrum in LDS; K <= 1024, the limit of dm_dnet_diffuse_f32.
+ *   dm_dnet_gradfeat_bwd_f32       recomputes gX, gY (the forward's gather chain), B_re, B_im and out = tanhf(gX B_re + gY B_im) with
+ *                         the forward's operations; p = fl(dO fl(1 - out^2)), U = fl(p gX), V = fl(p gY).
+ *                         dgX = (fl(p B_re) + U A_re) + V A_im, dgY = (fl(p B_im) - U A_im) + V A_re, each product one chain over
+ *                         ascending c (A_im null: dgX = fl(p B_re) + U A_re, dgY = fl(p B_im) + V A_re).
+ *                         dx = G_x^T dgX + G_y^T dgY as a gather over the rows of the transposed operators (row_len_t (B,N); cols_t,
+ *                         gx_t, gy_t (B,N,nnz_t), the union pattern of G_x^T and G_y^T in the layout of the forward's rows): entry
+ *                         q of row j adds gx_t dgX[col], then gy_t dgY[col], one fmaf each, q ascending.  The transposed rows are
+ *                         read only when dx is asked for.
+ *                         Per mesh dA_re_b = U^T gX + V^T gY, dA_im_b = V^T gX - U^T gY: four chains over ascending vertices, one
+ *                         sum or difference; then the meshes in ascending order.  Workspace dm_dnet_gradfeat_bwd_bytes(B, N, C):
+ *                         gX, gY, U, V, dgX, dgY (B,N,C) and the partials 2 (B,C,C).
+ * DM_EINVAL: the conditions of the forward counterpart; act = 1 without Y; K > 1024; dtimes without x; dx (gradfeat) without the
+ * transposed rows; dA_im without A_im; a null workspace. */
+int dm_dnet_linear_bwd_data_f32(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* dY, int lddy, const float* Y /*nullable*/, int ldy,
+                                int act, const float* W, int ldw, const int32_t* n_verts /*nullable*/, float* d0 /*nullable*/, int w0, int ld0,
+                                float* d1 /*nullable*/, int w1, int ld1, float* d2 /*nullable*/, int w2, int ld2);
+size_t dm_dnet_linear_bwd_bytes(int B, int C_out, int k_tot);
+int dm_dnet_linear_bwd_weight_f32(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* dY, int lddy, const float* Y /*nullable*/, int ldy,
+                                  int act, const float* src0, int w0, int ld0, const float* src1, int w1, int ld1, const float* src2, int w2,
+                                  int ld2, const int32_t* n_verts /*nullable*/, void* ws, float* dW /*nullable*/, int lddw, float* db /*nullable*/);
+size_t dm_dnet_diffuse_bwd_bytes(int B, int K, int C);
+int dm_dnet_diffuse_bwd_f32(dm_ctx* ctx, int B, int N, int K, int C, const float* dO, int lddo, const float* x /*nullable*/, int ldx,
+                            const float* mass, const float* evals, const float* evecs, int lde, const float* times,
+                            const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/, int lddx, float* dtimes /*nullable*/);
+size_t dm_dnet_gradfeat_bwd_bytes(int B, int N, int C);
+int dm_dnet_gradfeat_bwd_f32(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx,
+                             const float* gy, int nnz_t, const int32_t* row_len_t, const int32_t* cols_t, const float* gx_t, const float* gy_t,
+                             const float* dO, int lddo, const float* x, int ldx, const float* A_re, const float* A_im /*nullable*/, int lda,
+                             const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/, int lddx, float* dA_re /*nullable*/,
+                             float* dA_im /*nullable*/, int ldda);
+
 /* ---- heat-method geodesic distances ------------------------------------------------
  * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
  * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors
