@@ -1,6 +1,6 @@
 """
 MatchEngine, DiffusionNet: the operators of a batch of meshes, the forward pass, fp32 or -- for a halved module -- fp16 operands, and
-the backward pass of the fp32 kernels.
+the backward pass of the fp32 kernels and of the fp16 kernels (mixed precision: fp16 operands, float32 gradients).
 """
 import ctypes as C
 
@@ -370,6 +370,143 @@ class _DiffusionNetOps:
         dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
         ws = self._dnet_ws(self.lib.dm_dnet_gradfeat_bwd_bytes(Bn, N, Cw))
         self._chk(self.lib.dm_dnet_gradfeat_bwd_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t),
+                                                    _ptr(cols_t), _ptr(gx_t), _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
+                                                    _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
+        return dx, dAre, dAim
+
+    # ------------------------------------------------------------- DiffusionNet backward, fp16 operands (dm_dnet_*_bwd_f16)
+    def dnet_linear_backward_f16(self, grad_out, srcs, weight_h, y=None, n_verts=None, need_src=True, need_weight=True, need_bias=True, out=None):
+        """dnet_linear_backward on fp16 operands (dm_dnet_linear_bwd_data_f16, dm_dnet_linear_bwd_weight_f16): grad_out and y float32;
+        weight_h (C_out, sum w_s) float16, the rounded matrix the forward multiplied; every source float16 or float32 in its own dtype
+        (float32 elements are rounded as they are staged).  The gradients are float32; grad_weight belongs to the float32 master of
+        weight_h.  Arguments and the returned triple as dnet_linear_backward."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        flat = G.dim() == 2
+        if flat:
+            G = G.unsqueeze(0)
+        Bn, N, C_out = G.shape
+        srcs = [srcs] if isinstance(srcs, (torch.Tensor, int)) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError("dnet_linear_backward_f16: one to three sources")
+        widths = [int(s) if isinstance(s, int) else int(s.shape[-1]) for s in srcs]
+        need_src = [bool(need_src)] * len(srcs) if isinstance(need_src, bool) else [bool(f) for f in need_src]
+        if len(need_src) != len(srcs):
+            raise ValueError("dnet_linear_backward_f16: need_src has one flag per source")
+        W, ldw = (None, 0)
+        if any(need_src):
+            if weight_h is None:
+                raise ValueError("dnet_linear_backward_f16: the gradient of a source reads the weight")
+            W, ldw = self._strided(weight_h, torch.float16, "weight")
+            if W.dim() != 2 or tuple(W.shape) != (C_out, sum(widths)):
+                raise ValueError(f"dnet_linear_backward_f16: weight {tuple(W.shape)} does not match grad_out ({C_out}) and the summed source widths {sum(widths)}")
+        Y, ldy = (None, 0)
+        if y is not None:
+            Y, ldy = self._strided(y.unsqueeze(0) if flat else y, torch.float32, "y")
+            if tuple(Y.shape) != (Bn, N, C_out):
+                raise ValueError("dnet_linear_backward_f16: y must have the shape of grad_out")
+        nv = self._dnet_counts(n_verts, Bn)
+        act = 0 if Y is None else 1
+        d_src = [None] * len(srcs)
+        if any(need_src):
+            outs = [None] * len(srcs) if out is None else list(out)
+            a = []
+            for s, (w, need) in enumerate(zip(widths, need_src)):
+                if need:
+                    d_src[s], ld = self._dnet_out(None if outs[s] is None else (outs[s].unsqueeze(0) if flat else outs[s]), Bn, N, w,
+                                                  "dnet_linear_backward_f16")
+                    a.append((d_src[s], w, ld))
+                else:
+                    a.append((None, w, w))
+            a += [(None, 0, 0)] * (3 - len(a))
+            self._chk(self.lib.dm_dnet_linear_bwd_data_f16(self.ctx, Bn, N, C_out, len(srcs), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(W), ldw, _ptr(nv),
+                                                           _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2]))
+        dW = db = None
+        if need_weight or need_bias:
+            if any(isinstance(s, int) for s in srcs):
+                raise ValueError("dnet_linear_backward_f16: the weight and bias gradients read the sources")
+            mats = [self._strided(s.unsqueeze(0) if flat else s, _kept(s), "src") for s in srcs]
+            if any(tuple(m.shape[:2]) != (Bn, N) for m, _ in mats):
+                raise ValueError("dnet_linear_backward_f16: the sources differ from grad_out in their leading dimensions")
+            a = [(m, m.shape[2], ld, _flag(m)) for m, ld in mats] + [(None, 0, 0, _lib.DM_F32)] * (3 - len(mats))
+            dW = torch.empty((C_out, sum(widths)), dtype=torch.float32, device=self.device) if need_weight else None
+            db = torch.empty((C_out,), dtype=torch.float32, device=self.device) if need_bias else None
+            ws = self._dnet_ws(self.lib.dm_dnet_linear_bwd_f16_bytes(Bn, C_out, sum(widths)))
+            self._chk(self.lib.dm_dnet_linear_bwd_weight_f16(self.ctx, Bn, N, C_out, len(mats), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(a[0][0]), *a[0][1:],
+                                                             _ptr(a[1][0]), *a[1][1:], _ptr(a[2][0]), *a[2][1:], _ptr(nv), _ptr(ws), _ptr(dW), sum(widths),
+                                                             _ptr(db)))
+        if flat:
+            d_src = [None if d is None else d[0] for d in d_src]
+        return d_src, dW, db
+
+    def dnet_diffuse_backward_f16(self, grad_out, x, evecs_h, mevecs_h, e1, e2, evals, times, n_verts=None, need_x=True, need_times=True, out=None):
+        """The gradients of dnet_diffuse_f16 (dm_dnet_diffuse_bwd_f16) with respect to x and to the clamped times: grad_out, x (B,N,C)
+        float32 (x may be None with need_times=False), the operands as in dnet_diffuse_f16, times float32.  grad_x is dnet_diffuse_f16
+        of grad_out with the two matrix operands exchanged.  Returns (grad_x or None, grad_times or None), float32."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        E, lde = self._strided(evecs_h, torch.float16, "evecs_h")
+        M, ldm = self._strided(mevecs_h, torch.float16, "mevecs_h")
+        Bn, N, Cw = G.shape
+        K = E.shape[2]
+        X, ldx = (None, 0)
+        if need_times:
+            X, ldx = self._strided(x, torch.float32, "x")
+            if tuple(X.shape) != (Bn, N, Cw):
+                raise ValueError("dnet_diffuse_backward_f16: x must have the shape of grad_out")
+        evals = self._dev(evals, torch.float32, "evals")
+        times = self._dev(times, torch.float32, "times")
+        e1, e2 = self._dev(e1, torch.int32, "e1"), self._dev(e2, torch.int32, "e2")
+        if (tuple(E.shape[:2]) != (Bn, N) or M.shape != E.shape or tuple(evals.shape) != (Bn, K) or tuple(times.shape) != (Cw,)
+                or tuple(e1.shape) != (Bn,) or tuple(e2.shape) != (Bn,)):
+            raise ValueError("dnet_diffuse_backward_f16: grad_out (B,N,C), evecs_h / mevecs_h (B,N,K), e1 / e2 (B), evals (B,K), times (C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_diffuse_backward_f16") if need_x else (None, 0)
+        dt = torch.empty((Cw,), dtype=torch.float32, device=self.device) if need_times else None
+        ws = self._dnet_ws(self.lib.dm_dnet_diffuse_bwd_f16_bytes(Bn, K, Cw))
+        self._chk(self.lib.dm_dnet_diffuse_bwd_f16(self.ctx, Bn, N, K, Cw, _ptr(G), ldg, _ptr(X), ldx, _ptr(E), lde, _ptr(M), ldm, _ptr(e1), _ptr(e2),
+                                                   _ptr(evals), _ptr(times), _ptr(nv), _ptr(ws), _ptr(dx), lddx, _ptr(dt)))
+        return dx, dt
+
+    def dnet_gradient_features_backward_f16(self, grad_out, x, row_len, cols, gx, gy, rows_t, A_re_h, A_im_h=None, n_verts=None, need_x=True,
+                                            need_A=True, out=None):
+        """The gradients of dnet_gradient_features_f16 (dm_dnet_gradfeat_bwd_f16): A_re_h / A_im_h float16, the rounded matrices the forward
+        multiplied; everything else as dnet_gradient_features_backward.  Returns (grad_x or None, grad_A_re or None, grad_A_im or None),
+        float32; the matrix gradients belong to the float32 masters."""
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        if tuple(G.shape) != (Bn, N, Cw):
+            raise ValueError("dnet_gradient_features_backward_f16: grad_out must have the shape of x")
+        row_len = self._dev(row_len, torch.int32, "row_len")
+        cols = self._dev(cols, torch.int32, "cols")
+        gx = self._dev(gx, torch.float32, "gx")
+        gy = self._dev(gy, torch.float32, "gy")
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError("dnet_gradient_features_backward_f16: row_len (B,N), cols / gx / gy (B,N,nnz)")
+        rl_t = cols_t = gx_t = gy_t = None
+        nnz_t = 0
+        if need_x:
+            if rows_t is None:
+                raise ValueError("dnet_gradient_features_backward_f16: the gradient of x reads the transposed rows")
+            rl_t, cols_t = self._dev(rows_t[0], torch.int32, "row_len_t"), self._dev(rows_t[1], torch.int32, "cols_t")
+            gx_t, gy_t = self._dev(rows_t[2], torch.float32, "gx_t"), self._dev(rows_t[3], torch.float32, "gy_t")
+            if (cols_t.dim() != 3 or tuple(cols_t.shape[:2]) != (Bn, N) or gx_t.shape != cols_t.shape or gy_t.shape != cols_t.shape
+                    or tuple(rl_t.shape) != (Bn, N)):
+                raise ValueError("dnet_gradient_features_backward_f16: row_len_t (B,N), cols_t / gx_t / gy_t (B,N,nnz_t)")
+            nnz_t = cols_t.shape[2]
+        Are, lda = self._strided(A_re_h, torch.float16, "A_re")
+        Aim = None
+        if A_im_h is not None:
+            Aim, lda2 = self._strided(A_im_h, torch.float16, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError("dnet_gradient_features_backward_f16: A_re / A_im must be (C, C)")
+        nv = self._dnet_counts(n_verts, Bn)
+        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_backward_f16") if need_x else (None, 0)
+        dAre = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A else None
+        dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
+        ws = self._dnet_ws(self.lib.dm_dnet_gradfeat_bwd_f16_bytes(Bn, N, Cw))
+        self._chk(self.lib.dm_dnet_gradfeat_bwd_f16(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t),
                                                     _ptr(cols_t), _ptr(gx_t), _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
                                                     _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
         return dx, dAre, dAim

@@ -78,6 +78,13 @@ SIGNATURES = {
     "dm_dnet_linear_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _i, _i, _p, _i, _p, _i]),
     "dm_dnet_diffuse_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _i, _p, _p, _i]),
     "dm_dnet_gradfeat_f16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _i, _p, _p, _i, _p, _p, _i]),
+    "dm_dnet_linear_bwd_data_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _i, _p, _p, _i, _i, _p, _i, _i, _p, _i, _i]),
+    "dm_dnet_linear_bwd_f16_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_linear_bwd_weight_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _i, _i, _p, _p, _p, _i, _p]),
+    "dm_dnet_diffuse_bwd_f16_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_diffuse_bwd_f16": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
+    "dm_dnet_gradfeat_bwd_f16_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm_dnet_gradfeat_bwd_f16": (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _p, _i, _p, _p, _p, _i, _p, _p, _i]),
     "dm_heat_geodesic_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm_heat_geodesic_factor": (_i, [_p, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dm_heat_geodesic_solve": (_i, [_p, _i, _i, _i, _p, _i, _p, _p, _p]),

@@ -15,6 +15,13 @@ state_dict keys (a released checkpoint loads with strict=True), and two routes t
            dm_dnet_linear_bwd_weight_f32, dm_dnet_diffuse_bwd_f32, dm_dnet_gradfeat_bwd_f32 (diffusion_net/backward.py); dropout, the
            tail and the loss stay torch operations, so training mode works.  It needs a GPU, diffusion_method="spectral", float32
            parameters and inputs and k_eig <= 1024.
+           compute_dtype=torch.float16 (with route="device", differentiable=True) is mixed-precision training: the parameters stay
+           float32 masters, every matrix (nn.Linear.weight, A_re, A_im, A) is rounded to float16 once per call, the forward runs the
+           three fp16 kernels with float32 biases, times and intermediates, and the backward dm_dnet_linear_bwd_data_f16 /
+           dm_dnet_linear_bwd_weight_f16, dm_dnet_diffuse_bwd_f16, dm_dnet_gradfeat_bwd_f16: fp16 matrix operands, fp32 accumulation,
+           float32 gradients for the masters.  Inputs are float32, or float16 where they do not require grad.  The route does no loss
+           scaling: a gradient entry below fp16's range is lost where it is staged as a matrix operand and one beyond 65504 becomes
+           infinite, so torch.amp.GradScaler is used exactly as with torch.autocast.  A module after .half() stays refused.
 route="auto" takes the device route where those conditions hold and tools/dnet_forward_time.py measured it faster (AUTO_DEVICE below),
 else torch; it never takes the differentiable device route (route="torch" and route="auto" ignore differentiable=).  The outputs_at / last_activation tail is the same torch code behind both.
 
@@ -22,7 +29,7 @@ The device route reads the operators from a PackedOperators (pack_operators): fp
 of gradX / gradY, built once per mesh set and passed as operators=; given the reference's tensors instead, forward packs them per call.
 DiffusionNet.forward_many runs a ragged list of meshes as one batched device call.
 
-Not built on the device: a backward for the fp16 kernels, implicit_dense, point clouds (their operators are not built either).
+Not built on the device: gradients of a module after .half() (fp16 parameters without masters), bf16, implicit_dense, point clouds (their operators are not built either).
 """
 import torch
 import torch.nn as nn
@@ -359,9 +366,10 @@ class DiffusionNet(nn.Module):
         self.last_route = None          # the route the last forward took ("torch" or "device")
 
     # ------------------------------------------------------------------ routes
-    def _device_obstacle(self, xs, extra=(), differentiable=False, k_eig=None):
+    def _device_obstacle(self, xs, extra=(), differentiable=False, k_eig=None, mixed=False):
         """None when the device route can run for these inputs, else the condition that keeps it from running.  differentiable: the
-        route that records the autograd graph (training mode and tensors that require grad are no obstacles; float32 only)"""
+        route that records the autograd graph (training mode and tensors that require grad are no obstacles; float32 only).  mixed:
+        its fp16 family (compute_dtype=torch.float16): float32 parameters; inputs float32, or float16 where they do not require grad"""
         if not torch.cuda.is_available():
             return "it needs a ROCm GPU (gfx950)"
         if any(not x.is_cuda for x in xs):
@@ -371,9 +379,9 @@ class DiffusionNet(nn.Module):
         if self.training and self.dropout and not differentiable:
             return "the module must be in eval mode or built with dropout=False"
         params = list(self.parameters())
-        if differentiable and any(t.dtype != torch.float32 for t in list(xs) + params):
+        if differentiable and any(t.dtype != torch.float32 for t in (params if mixed else list(xs) + params)):
             return "the parameters and inputs must be float32 (the fp16 kernels have no backward)"
-        why = self._dtype_obstacle(xs)
+        why = self._mixed_input_obstacle(xs) if differentiable and mixed else self._dtype_obstacle(xs)
         if why is not None:
             return why
         if any(not p.is_cuda for p in params):
@@ -390,6 +398,23 @@ class DiffusionNet(nn.Module):
         if kinds == {torch.float16}:
             return None if all(x.dtype in (torch.float16, torch.float32) for x in xs) else "with float16 parameters every input must be float16 or float32"
         return "the parameters must be all float32 or all float16, not " + ", ".join(sorted(str(k)[6:] for k in kinds))
+
+    @staticmethod
+    def _mixed_input_obstacle(xs):
+        """compute_dtype=torch.float16: None for float32 inputs and float16 inputs that do not require grad, else what is wrong"""
+        for x in xs:
+            if x.dtype not in (torch.float16, torch.float32):
+                return "with compute_dtype=torch.float16 every input must be float32 or float16, not " + str(x.dtype)[6:]
+            if x.dtype == torch.float16 and x.requires_grad:
+                return "with compute_dtype=torch.float16 a float16 input must not require grad (the input gradient is float32)"
+        return None
+
+    @staticmethod
+    def _mixed(compute_dtype):
+        """whether compute_dtype asks for the fp16 family of the differentiable device route; ValueError for what it cannot be"""
+        if compute_dtype is not None and compute_dtype != torch.float16:
+            raise ValueError("compute_dtype must be None or torch.float16, not {}".format(compute_dtype))
+        return compute_dtype is not None
 
     def is_half(self):
         return self.first_lin.weight.dtype == torch.float16
@@ -415,22 +440,25 @@ class DiffusionNet(nn.Module):
         return {"first": (self.first_lin.weight.data, self.first_lin.bias.data), "last": (self.last_lin.weight.data, self.last_lin.bias.data),
                 "blocks": [b.device_weights() for b in self.blocks]}
 
-    def _run_device(self, xs, packed, differentiable=False):
+    def _run_device(self, xs, packed, differentiable=False, mixed=False):
         from ..engine import default_engine
         eng = default_engine(xs[0].device)
         if packed.device != eng.device:
             packed = packed.to(eng.device)
         if differentiable:
-            return run_differentiable(self, eng, xs, packed)
+            return run_differentiable(self, eng, xs, packed, half=mixed)
         with torch.no_grad():
             return eng.diffusion_net_forward(self.device_weights(), packed, xs if len(xs) > 1 else xs[0])
 
     def forward(self, x_in, mass=None, L=None, evals=None, evecs=None, gradX=None, gradY=None, edges=None, faces=None, *, route="auto", operators=None,
-                differentiable=False):
+                differentiable=False, compute_dtype=None):
         """x_in (N,C_in) or (B,N,C_in), or a tuple of up to three such tensors read as concatenated along the channels; mass (N) / (B,N),
         L, evals (K), evecs (N,K), gradX, gradY sparse (N,N) (or with the batch dimension), edges / faces for outputs_at.
         operators: a PackedOperators of the B meshes (device route; mass may then be None).  differentiable: with route="device", record
-        the autograd graph through the backward kernels (module docstring); ignored by route="torch" and route="auto".  Returns (N,C_out) or (B,N,C_out), or what
+        the autograd graph through the backward kernels (module docstring); ignored by route="torch" and route="auto".
+        compute_dtype: None, or torch.float16 -- with route="device", differentiable=True the mixed-precision family (float32 master
+        parameters, fp16 matrix operands, float32 gradients; no loss scaling of its own: use torch.amp.GradScaler as with
+        torch.autocast); ignored like differentiable=; any other dtype is a ValueError.  Returns (N,C_out) or (B,N,C_out), or what
         outputs_at makes of it."""
         xs = list(x_in) if isinstance(x_in, (tuple, list)) else [x_in]
         if not 1 <= len(xs) <= 3:
@@ -445,8 +473,9 @@ class DiffusionNet(nn.Module):
             xs = [x.unsqueeze(0) for x in xs]
             mass, L, evals, evecs, gradX, gradY, edges, faces = (up(t) for t in (mass, L, evals, evecs, gradX, gradY, edges, faces))
         differentiable = bool(differentiable) and route == "device"
+        mixed = self._mixed(compute_dtype) and differentiable
         k_eig = operators.evals.shape[-1] if operators is not None else (None if evals is None else evals.shape[-1])
-        picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs), differentiable, k_eig),
+        picked = _routes.pick_torch(route, "DiffusionNet", lambda: self._device_obstacle(xs, (mass, evals, evecs), differentiable, k_eig, mixed),
                                     AUTO_DEVICE[("batch" if xs[0].shape[0] > 1 else "single") + ("_half" if self.is_half() else "")], refusal=RuntimeError)
         self.last_route = picked
         if picked == "torch":
@@ -465,20 +494,21 @@ class DiffusionNet(nn.Module):
                                          for b in range(Bn)], device=xs[0].device)
             if len(packed.n_verts) != xs[0].shape[0] or packed.mass.shape[1] != xs[0].shape[1]:
                 raise ValueError("operators: packed for {} meshes of up to {} vertices, x_in is {}".format(len(packed.n_verts), packed.mass.shape[1], tuple(xs[0].shape)))
-            x = self._run_device(xs, packed, differentiable)
+            x = self._run_device(xs, packed, differentiable, mixed)
             if mass is None:
                 mass = packed.mass
         x_out = self._tail(x, mass, edges, faces)
         return x_out.squeeze(0) if flat else x_out
 
-    def forward_many(self, x_list, packed, edges=None, faces=None, differentiable=False):
+    def forward_many(self, x_list, packed, edges=None, faces=None, differentiable=False, compute_dtype=None):
         """A ragged list of meshes as ONE batched device call: x_list[b] (n_b, C_in), or a tuple of up to three such tensors per mesh;
         packed: the PackedOperators of the same meshes.  Returns the list of outputs, each what forward() returns for its mesh alone
-        (edges / faces: lists, for outputs_at).  differentiable: as in forward."""
+        (edges / faces: lists, for outputs_at).  differentiable, compute_dtype: as in forward with route="device"."""
         per = [list(x) if isinstance(x, (tuple, list)) else [x] for x in x_list]
         if len(per) != len(packed.n_verts) or any(p[0].shape[0] != n for p, n in zip(per, packed.n_verts)):
             raise ValueError("forward_many: x_list does not match the packed meshes")
-        why = self._device_obstacle([x for p in per for x in p], (), bool(differentiable), packed.evals.shape[-1])
+        mixed = self._mixed(compute_dtype) and bool(differentiable)
+        why = self._device_obstacle([x for p in per for x in p], (), bool(differentiable), packed.evals.shape[-1], mixed)
         if why is not None:
             raise RuntimeError("DiffusionNet.forward_many: " + why)
         self.last_route = "device"
@@ -491,7 +521,7 @@ class DiffusionNet(nn.Module):
             xs.append(buf)
         if sum(x.shape[-1] for x in xs) != self.C_in:
             raise ValueError("DiffusionNet was constructed with C_in={}, but x_list has last dim={}".format(self.C_in, sum(x.shape[-1] for x in xs)))
-        x = self._run_device(xs, packed, bool(differentiable))
+        x = self._run_device(xs, packed, bool(differentiable), mixed)
         mass = packed.mass.to(x.device)
         return [self._tail(x[b:b + 1, :n], mass[b:b + 1, :n], None if edges is None else edges[b].unsqueeze(0),
                            None if faces is None else faces[b].unsqueeze(0)).squeeze(0) for b, n in enumerate(packed.n_verts)]

@@ -138,7 +138,7 @@ class MeshFeaturizer(nn.Module):
         return [o[5] for o in outs], [(o[1].R, o[1].T) for o in outs]
 
     def forward(self, mesh_raw, mesh_simp, operators, cameras, return_mvfeatures=False, *, fts=None, pix2face=None, route="auto", fts_lr=None,
-                images=None, raw=None, backbone=None, image_size=None, differentiable=False):
+                images=None, raw=None, backbone=None, image_size=None, differentiable=False, compute_dtype=None):
         """mesh_simp: the simplified mesh (verts_list()[0] / faces_list()[0], or a (verts, faces) pair); mesh_raw is the rendering half's
         and is not read.  operators: the tuple of get_operators (frames, massvec, L, evals, evecs, gradX, gradY), or a PackedOperators of
         this one mesh.  cameras (R, T): the cameras the maps fts (views, C, H, W) were rendered with; pix2face: optional, another
@@ -149,7 +149,8 @@ class MeshFeaturizer(nn.Module):
         `cameras` (generated from num_views when None) at image_size (default: the extractor's size, else 512), the images go to the
         backbone and the result takes the raw= route with images=.
         differentiable: passed to extractor_3d (DiffusionNet.forward): with route='device' the refiner records its autograd graph
-        through the backward kernels, so a training step stays on the device route.
+        through the backward kernels, so a training step stays on the device route.  compute_dtype: passed along with it; torch.float16
+        selects the mixed-precision kernels (float32 master parameters, fp16 matrix operands; use torch.amp.GradScaler as with autocast).
         Returns the row-normalised features (V, width); with return_mvfeatures also the unnormalised ones and the (V, C) multi-view features."""
         _routes.check(route, _routes.HOST)
         if fts is None and fts_lr is None and raw is None and backbone is not None:
@@ -171,20 +172,22 @@ class MeshFeaturizer(nn.Module):
                 raise ValueError("forward takes one mesh: a PackedOperators of several meshes goes to forward_many")
             packed = operators.to(self.device) if operators.device != self.device else operators
             sources = (lifted,) + self._neck(verts, packed.evals[0], packed.evecs[0, :verts.shape[0]])
-            raw = self.extractor_3d(sources, route=net_route, operators=packed, differentiable=differentiable)
+            raw = self.extractor_3d(sources, route=net_route, operators=packed, differentiable=differentiable, compute_dtype=compute_dtype)
         else:
             ops = [None if op is None else op.to(self.device) for op in operators]       # frames, mass, L, evals, evecs, gradX, gradY
             sources = (lifted,) + self._neck(verts, ops[3], ops[4])
-            raw = self.extractor_3d(sources, ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], route=net_route, differentiable=differentiable)
+            raw = self.extractor_3d(sources, ops[1], ops[2], ops[3], ops[4], ops[5], ops[6], route=net_route, differentiable=differentiable,
+                                    compute_dtype=compute_dtype)
         unit = self._normalize(raw)
         return (unit, raw, lifted) if return_mvfeatures else unit
 
     def forward_many(self, meshes_raw, meshes_simp, packed, cameras_list, return_mvfeatures=False, *, fts_list=None, pix2face_list=None,
-                     fts_lr=None, images=None, raw=None, backbone=None, image_size=None):
+                     fts_lr=None, images=None, raw=None, backbone=None, image_size=None, differentiable=False, compute_dtype=None):
         """forward for a ragged list of meshes on the device: ONE batched lifting call and ONE batched DiffusionNet call.  packed: the
         PackedOperators of the same meshes (diffusion_net.layers.pack_operators).  Returns the list of what forward returns per mesh.
         Without fts_list: fts_lr / images, lists of (views_b, C, h, w) and (views_b, 3, H, W), go through the upsampler on the device; or raw, a list of (s3, s4, s5, dino) per mesh, through the aggregation network first;
-        or backbone=, as in forward: the raw meshes are rendered in ONE device call (cameras_list entries may be None)."""
+        or backbone=, as in forward: the raw meshes are rendered in ONE device call (cameras_list entries may be None).
+        differentiable, compute_dtype: passed to extractor_3d.forward_many, as in forward."""
         if fts_list is None and fts_lr is None and raw is None and backbone is not None:
             with torch.no_grad():
                 images, cameras_list = self._render_views(list(meshes_raw), list(cameras_list), "device", image_size)
@@ -211,7 +214,7 @@ class MeshFeaturizer(nn.Module):
             if verts.shape[0] != packed.n_verts[b]:
                 raise ValueError(f"forward_many: mesh {b} has {verts.shape[0]} vertices, its packed operators {packed.n_verts[b]}")
             xs.append((mv[b],) + self._neck(verts, packed.evals[b], packed.evecs[b, :verts.shape[0]]))
-        outs = self.extractor_3d.forward_many(xs, packed)
+        outs = self.extractor_3d.forward_many(xs, packed, differentiable=differentiable, compute_dtype=compute_dtype)
         if return_mvfeatures:
             return [(self._normalize(o), o, m) for o, m in zip(outs, mv)]
         return [self._normalize(o) for o in outs]

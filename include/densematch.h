@@ -645,6 +645,61 @@ int dm_dnet_gradfeat_bwd_f32(dm_ctx* ctx, int B, int N, int C, int nnz, const in
                              const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/, int lddx, float* dA_re /*nullable*/,
                              float* dA_im /*nullable*/, int ldda);
 
+/* ---- DiffusionNet backward pass (training), fp16 operands ------------------------------
+ * Mixed-precision training: the gradients of the three fp16 forward entries with respect to their activations and to the fp32 MASTER
+ * parameters whose fp16 roundings the forward multiplied (W, A_re, A_im fp16 here, rounded by the caller once per step).  Every product
+ * is exact fp16 x fp16 accumulated in fp32 on v_mfma_f32_32x32x16_f16, the contraction index in ascending chunks of 16 from a zero
+ * accumulator, never split, no atomics.  Operands behind a mesh's rows, a matrix's columns or a row's ELL slots are staged as zeros.  A
+ * value is rounded to fp16 (to nearest even; beyond 65504 infinite) once, at the places marked ROUNDED below and nowhere else: a
+ * gradient entry below fp16's range is lost there and one beyond it becomes infinite -- loss scaling is the caller's.  Gradients of
+ * activations travel between the kernels in fp32.
+ * Order guarantees.
+ *   - A gradient with respect to an activation depends on its own row and column of the operands only: the same bits alone and in any
+ *     batch, whatever tile the element falls in (every product runs in 64 x 64 tiles; no launch picks another shape).
+ *   - A gradient with respect to a parameter is ONE fp32 chain per mesh over ascending vertices (into the workspace); then the meshes
+ *     are added ((P_0 + P_1) + P_2) + .. in fp32.  It is fp32 and belongs to the fp32 master parameter: the rounding of the matrix is
+ *     passed straight through.
+ * Workspace, n_verts and null outputs as for the fp32 entries.  fp16 operands need 2-byte alignment only; dtype flags are DM_F16 | DM_F32.
+ *   dm_dnet_linear_bwd_data_f16    dZ = dY * [Y > 0] (act = 1, Y the saved fp32 output) or dZ = dY, ROUNDED as it is staged.
+ *                         d_s = dZ W_h[:, off_s : off_s + w_s] over ascending o; W_h (C_out, K_tot) fp16 is read where it lies.  Outputs
+ *                         fp32, one per source with its own leading dimension; a null d_s skips that source.
+ *   dm_dnet_linear_bwd_weight_f16  P_b[o, off_s + k] = sum_i fp16(dZ[b,i,o]) fp16(src_s[b,i,k]): an fp32 source (dtype_s) is ROUNDED as
+ *                         it is staged -- the value the forward multiplied -- and an fp16 source is read as it is.  Column K_tot is the
+ *                         bias: the same product against the constant 1.  The loads of two stages of the vertex contraction are in
+ *                         flight.  dW (C_out, K_tot), db (C_out) fp32.  Workspace dm_dnet_linear_bwd_f16_bytes(B, C_out, K_tot).
+ *   dm_dnet_diffuse_bwd_f16        dx = M Phi (coef * Phi^T dO): dm_dnet_diffuse_f16 itself with evecs_h / mevecs_h and e1 / e2
+ *                         exchanged -- its roundings (dO as staged; the spectrum once, at the scale 2^(14 - e1 - e2), from the exact
+ *                         float64 product) and its bits.  dtimes: g = evecs_h^T fp16(dO), s = mevecs_h^T fp16(x), fp32 accumulators
+ *                         over ascending vertices; T[b,k,c] = evals coef g s 2^-(e1 + e2) formed in float64 and rounded once to fp32;
+ *                         dtimes[c] = -((m_0 + m_1) + ..), m_b the ascending-k sum of T[b,.,c]; with respect to the clamped time.  x
+ *                         is read for dtimes only.  Workspace dm_dnet_diffuse_bwd_f16_bytes(B, K, C): T.  K <= 1024.
+ *   dm_dnet_gradfeat_bwd_f16       gX, gY from the fp32 gather chain; B_re, B_im and out recomputed with dm_dnet_gradfeat_f16's
+ *                         operations; p = fl(dO fl(1 - out^2)), U = fl(p gX), V = fl(p gY) in fp32.  U, V, gX, gY are ROUNDED only as
+ *                         matrix operands: of the products with A_h (dgX = (fl(p B_re) + U A_re) + V A_im,
+ *                         dgY = (fl(p B_im) - U A_im) + V A_re, assembled in fp32 in the fp32 entry's order) and of
+ *                         dA_re_b = U^T gX + V^T gY, dA_im_b = V^T gX - U^T gY.  dx is the fp32 gather over the transposed rows.
+ *                         A_im nullable.  Workspace dm_dnet_gradfeat_bwd_f16_bytes(B, N, C).
+ * DM_EINVAL: the conditions of the fp32 entries; also an unknown dtype flag, an operand not aligned to its element, a null workspace. */
+int dm_dnet_linear_bwd_data_f16(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* dY, int lddy, const float* Y /*nullable*/, int ldy,
+                                int act, const void* W, int ldw, const int32_t* n_verts /*nullable*/, float* d0 /*nullable*/, int w0, int ld0,
+                                float* d1 /*nullable*/, int w1, int ld1, float* d2 /*nullable*/, int w2, int ld2);
+size_t dm_dnet_linear_bwd_f16_bytes(int B, int C_out, int k_tot);
+int dm_dnet_linear_bwd_weight_f16(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* dY, int lddy, const float* Y /*nullable*/, int ldy,
+                                  int act, const void* src0, int w0, int ld0, int dtype0, const void* src1, int w1, int ld1, int dtype1,
+                                  const void* src2, int w2, int ld2, int dtype2, const int32_t* n_verts /*nullable*/, void* ws,
+                                  float* dW /*nullable*/, int lddw, float* db /*nullable*/);
+size_t dm_dnet_diffuse_bwd_f16_bytes(int B, int K, int C);
+int dm_dnet_diffuse_bwd_f16(dm_ctx* ctx, int B, int N, int K, int C, const float* dO, int lddo, const float* x /*nullable*/, int ldx,
+                            const void* evecs_h, int lde, const void* mevecs_h, int ldm, const int32_t* e1, const int32_t* e2, const float* evals,
+                            const float* times, const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/, int lddx,
+                            float* dtimes /*nullable*/);
+size_t dm_dnet_gradfeat_bwd_f16_bytes(int B, int N, int C);
+int dm_dnet_gradfeat_bwd_f16(dm_ctx* ctx, int B, int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx,
+                             const float* gy, int nnz_t, const int32_t* row_len_t, const int32_t* cols_t, const float* gx_t, const float* gy_t,
+                             const float* dO, int lddo, const float* x, int ldx, const void* A_re, const void* A_im /*nullable*/, int lda,
+                             const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/, int lddx, float* dA_re /*nullable*/,
+                             float* dA_im /*nullable*/, int ldda);
+
 /* ---- heat-method geodesic distances ------------------------------------------------
  * Replaces pyFM's heat method (pyFM/mesh/geometry.py:587-740 heat_geodesic_from / heat_geodmat, behind
  * TriMesh.get_geodesic(robust=False) / geod_from(i, robust=False), pyFM/mesh/trimesh.py:612-738), where SciPy's SuperLU factors

@@ -15,6 +15,13 @@ then five timed windows taken alternately between the routes; a window is `reps`
 clock, and the figure is the median window over reps.  The two routes' gradients are compared first (per tensor max |device - torch| /
 max |torch|, the largest).  Then one profiled device step: milliseconds and share per kernel name, and the TFLOP/s of the two linear
 backward kernels (2 rows C_out sum w each per layer).  Prints one JSON line.
+
+    python tools/dnet_train_time.py --mixed [--meshes 16] [--out result.json]
+
+--mixed times three arms instead, windows taken alternately in the same way: the mixed-precision device route (compute_dtype=
+torch.float16: float32 masters, the fp16 forward kernels, dm_dnet_*_bwd_f16), the fp32 differentiable device route, and the torch route
+under torch.autocast("cuda", dtype=torch.float16).  It profiles one mixed step per kernel name and reports the largest workspace the
+backward entries ask for at this configuration.
 """
 import argparse
 import json
@@ -45,6 +52,7 @@ def main():
     ap.add_argument("--k-eig", type=int, default=128)
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--blocks", type=int, default=8)
+    ap.add_argument("--mixed", action="store_true", help="time the mixed-precision route against the fp32 device route and torch autocast")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -83,7 +91,46 @@ def main():
     result = {"tool": "tools/dnet_train_time.py", "meshes": a.meshes, "vertices": n, "k_eig": a.k_eig, "width": a.width, "blocks": a.blocks,
               "C_in": list(widths), "gpu": torch.cuda.get_device_name(0)}
     per_row = 2 * (sum(widths) * a.width + a.blocks * (3 * a.width * a.width + 2 * a.width * a.width) + a.width * a.width)      # linears, FLOP
-    for name, (idx, packed, reps) in cases.items():
+    for name, (idx, packed, reps) in cases.items() if a.mixed else ():
+        many = lambda **kw: step(lambda: net.forward_many([xs[i] for i in idx], packed, differentiable=True, **kw), idx)
+        mixed_step, fp32_step = (lambda: many(compute_dtype=torch.float16)), (lambda: many())
+
+        def autocast_step():
+            with torch.autocast("cuda", dtype=torch.float16):
+                outs = torch_outputs(idx)
+            step(lambda: [y.float() for y in outs], idx)
+        arms = {"mixed": mixed_step, "device_fp32": fp32_step, "torch_autocast": autocast_step}
+        fp32_step()
+        g32 = grads()
+        mixed_step()
+        gm = grads()
+        diff = {k: float((gm[k] - g32[k]).abs().max() / g32[k].abs().max()) for k in g32}
+        worst = max(diff, key=diff.get)
+        for _ in range(2):
+            for fn in arms.values():
+                fn()
+        times = {k: [] for k in arms}
+        for _ in range(5):
+            for k, fn in arms.items():
+                times[k].append(window(fn, reps))
+        entry = {k + "_ms": round(statistics.median(v), 3) for k, v in times.items()}
+        entry.update({k + "_ms_all": [round(t, 3) for t in v] for k, v in times.items()})
+        entry.update({"max_rel_grad_diff_mixed_vs_fp32": diff[worst], "max_rel_grad_diff_at": worst})
+        eng.profile_kernel("*")
+        mixed_step()
+        torch.cuda.synchronize()
+        report = eng.profile_report()
+        eng.profile_kernel(None)
+        total = sum(ms for _, ms in report.values())
+        entry["kernels_ms"] = {k: round(ms, 3) for k, (_, ms) in report.items()}
+        entry["kernels_share"] = {k: round(ms / total, 3) for k, (_, ms) in report.items()}
+        entry["kernels_launches"] = {k: int(c) for k, (c, _) in report.items()}
+        Bn, w = len(idx), a.width
+        entry["workspace_bytes"] = {"linear": int(eng.lib.dm_dnet_linear_bwd_f16_bytes(Bn, w, max(sum(widths), 3 * w))),
+                                    "diffuse": int(eng.lib.dm_dnet_diffuse_bwd_f16_bytes(Bn, a.k_eig, w)),
+                                    "gradfeat": int(eng.lib.dm_dnet_gradfeat_bwd_f16_bytes(Bn, n, w))}
+        result[name] = entry
+    for name, (idx, packed, reps) in () if a.mixed else cases.items():
         device_step = lambda: step(lambda: net.forward_many([xs[i] for i in idx], packed, differentiable=True), idx)
         torch_step = lambda: step(lambda: torch_outputs(idx), idx)
         device_step()
