@@ -17,7 +17,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 LIB = os.path.join(HERE, "libdensematch.so")
-SOURCES = ["dm_ctx.hip", "dm_p2p.hip", "dm_fmap.hip", "dm_project.hip", "dm_zoomout.hip", "dm_zoomfuse.hip", "dm_icp.hip", "dm_simnn.hip", "dm_knnsplit.hip", "dm_energy.hip", "dm_assign.hip", "dm_lsa_gather.hip", "dm_precise.hip", "dm_eigen.hip", "dm_peaks.hip", "dm_lbfgs.hip", "dm_fitfuse.hip", "dm_laplacian.hip", "dm_geodesic.hip", "dm_fps.hip", "dm_zoomsub.hip", "dm_graphgeod.hip", "dm_signatures.hip", "dm_orient.hip", "dm_mapmetrics.hip", "dm_fmn.hip", "dm_shapediff.hip", "dm_dnet.hip", "dm_dnet_layers.hip", "dm_dnet_bwd.hip", "dm_dnet_half.hip", "dm_dnet_half_bwd.hip", "dm_lift.hip", "dm_render.hip", "dm_jbu.hip", "dm_aggre.hip", "dm_vit.hip"]
+SOURCES = ["dm_ctx.hip", "dm_p2p.hip", "dm_fmap.hip", "dm_project.hip", "dm_zoomout.hip", "dm_zoomfuse.hip", "dm_icp.hip", "dm_simnn.hip", "dm_knnsplit.hip", "dm_energy.hip", "dm_assign.hip", "dm_lsa_gather.hip", "dm_precise.hip", "dm_eigen.hip", "dm_peaks.hip", "dm_lbfgs.hip", "dm_fitfuse.hip", "dm_laplacian.hip", "dm_geodesic.hip", "dm_fps.hip", "dm_zoomsub.hip", "dm_graphgeod.hip", "dm_signatures.hip", "dm_orient.hip", "dm_mapmetrics.hip", "dm_fmn.hip", "dm_shapediff.hip", "dm_dnet.hip", "dm_dnet_layers.hip", "dm_dnet_bwd.hip", "dm_dnet_half.hip", "dm_dnet_half_bwd.hip", "dm_lift.hip", "dm_render.hip", "dm_jbu.hip", "dm_jbu_bwd.hip", "dm_aggre.hip", "dm_vit.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-I", os.path.join(REPO, "include"), "-I", CSRC]
 

@@ -1,6 +1,7 @@
 """
 MatchEngine, guided feature upsampling (FeatUp's JBUStack at inference): the combined 7 x 7 kernels of a stage (dm_jbu_filters_f32), the
-fused bicubic upsampling + reflect padding + adaptive convolution (dm_jbu_apply), and the four stages with the final 1x1 convolution
+fused bicubic upsampling + reflect padding + adaptive convolution (dm_jbu_apply), its two gradients (dm_jbu_apply_bwd_filters_f32,
+dm_jbu_apply_bwd_source_f32: what featup.backward chains into autograd), and the four stages with the final 1x1 convolution
 (dm_dnet_linear_f32 on pixels as rows).  Filters and apply stay separate entry points: evaluating the last stage only where lifting
 samples it needs exactly that split.
 """
@@ -18,6 +19,21 @@ def _flag(dtype):
 
 
 class _JbuOps:
+    def _jbu_operand(self, t, what, dtypes):
+        """a 4-d operand the kernels read through element strides: on the device, in one of `dtypes` (else float32), where it lies
+        unless a stride is negative"""
+        t = t if isinstance(t, torch.Tensor) else torch.as_tensor(t)
+        if t.dim() != 4:
+            raise ValueError(f"{what}, got {tuple(t.shape)}")
+        if t.dtype not in dtypes:
+            t = t.to(torch.float32)
+        if t.device != self.device:
+            t = t.to(self.device)
+        if any(s < 0 for s in t.stride()):
+            t = t.contiguous()
+        self._check_stream()
+        return t
+
     def jbu_filters(self, guidance, params):
         """dm_jbu_filters_f32: guidance (B, 3, H, W), already at the stage's output size; params the packed block of the stage
         (featup.upsamplers.JBULearnedRange.packed).  Returns the kernels (B, H, W, 49) fp32."""
@@ -36,16 +52,7 @@ class _JbuOps:
         """dm_jbu_apply: source (B, C, h, w) fp16 | fp32 in any strides (read where it lies), filters (B, 2h, 2w, 49) fp32.
         out: an optional (B, C, 2h, 2w) fp32 | fp16 device tensor in any strides that give every element its own address (written where
         it lies); without it a new one of out_dtype, NCHW, or NCHW-shaped over channels-last memory."""
-        src = source if isinstance(source, torch.Tensor) else torch.as_tensor(source)
-        if src.dim() != 4:
-            raise ValueError(f"jbu_apply: source must be (B, C, h, w), got {tuple(src.shape)}")
-        if src.dtype not in (torch.float16, torch.float32):
-            src = src.to(torch.float32)
-        if src.device != self.device:
-            src = src.to(self.device)
-        if any(s < 0 for s in src.stride()):
-            src = src.contiguous()
-        self._check_stream()
+        src = self._jbu_operand(source, "jbu_apply: source must be (B, C, h, w)", (torch.float16, torch.float32))
         Bn, Cw, h, w = src.shape
         filt = self._dev(filters, torch.float32, "filters")
         if tuple(filt.shape[:3]) != (Bn, 2 * h, 2 * w) or filt.numel() != Bn * 4 * h * w * 49:
@@ -63,6 +70,38 @@ class _JbuOps:
         self._chk(self.lib.dm_jbu_apply(self.ctx, Bn, Cw, h, w, _flag(src.dtype), _ptr(src), *src.stride(), _ptr(filt), _flag(out.dtype), _ptr(out),
                                         *out.stride()))
         return out
+
+    def jbu_apply_bwd_filters(self, grad_out, source):
+        """dm_jbu_apply_bwd_filters_f32: the gradient of jbu_apply's output with respect to its filters.  grad_out (B, C, 2h, 2w) fp32
+        and source (B, C, h, w) fp16 | fp32, both in any strides and read where they lie -- the all-zero strides of the expanded
+        scalar that out.sum().backward() hands over included: the kernels only read it.  Returns (B, 2h, 2w, 49) fp32."""
+        src = self._jbu_operand(source, "jbu_apply_bwd_filters: source must be (B, C, h, w)", (torch.float16, torch.float32))
+        Bn, Cw, h, w = src.shape
+        g = self._jbu_operand(grad_out, f"jbu_apply_bwd_filters: grad_out must be ({Bn}, {Cw}, {2 * h}, {2 * w})", (torch.float32,))
+        if tuple(g.shape) != (Bn, Cw, 2 * h, 2 * w):
+            raise ValueError(f"jbu_apply_bwd_filters: grad_out must be ({Bn}, {Cw}, {2 * h}, {2 * w}) for a source {tuple(src.shape)}, "
+                             f"got {tuple(g.shape)}")
+        gfilt = torch.empty((Bn, 2 * h, 2 * w, 49), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.dm_jbu_apply_bwd_filters_f32(self.ctx, Bn, Cw, h, w, _flag(src.dtype), _ptr(src), *src.stride(), _ptr(g), *g.stride(),
+                                                        _ptr(gfilt)))
+        return gfilt
+
+    def jbu_apply_bwd_source(self, grad_out, filters, out_dtype=torch.float32):
+        """dm_jbu_apply_bwd_source_f32: the gradient of jbu_apply's output with respect to its source.  grad_out (B, C, 2h, 2w) fp32 in
+        any strides, read where it lies (see jbu_apply_bwd_filters); filters (B, 2h, 2w, 49) fp32.  Returns (B, C, h, w), NCHW: fp32
+        as the kernel writes it, or that rounded to out_dtype=torch.float16 with torch."""
+        if out_dtype not in (torch.float16, torch.float32):
+            raise ValueError("jbu_apply_bwd_source: out_dtype must be torch.float32 or torch.float16")
+        g = self._jbu_operand(grad_out, "jbu_apply_bwd_source: grad_out must be (B, C, 2h, 2w)", (torch.float32,))
+        Bn, Cw, H, W = g.shape
+        if H % 2 or W % 2 or H < 4 or W < 4:
+            raise ValueError(f"jbu_apply_bwd_source: grad_out must be (B, C, 2h, 2w) with h, w >= 2, got {tuple(g.shape)}")
+        filt = self._dev(filters, torch.float32, "filters")
+        if tuple(filt.shape[:3]) != (Bn, H, W) or filt.numel() != Bn * H * W * 49:
+            raise ValueError(f"jbu_apply_bwd_source: filters must be ({Bn}, {H}, {W}, 49) for a grad_out {tuple(g.shape)}, got {tuple(filt.shape)}")
+        gsrc = torch.empty((Bn, Cw, H // 2, W // 2), dtype=torch.float32, device=self.device)
+        self._chk(self.lib.dm_jbu_apply_bwd_source_f32(self.ctx, Bn, Cw, H // 2, W // 2, _ptr(g), *g.stride(), _ptr(filt), _ptr(gsrc)))
+        return gsrc if out_dtype == torch.float32 else gsrc.to(out_dtype)
 
     def jbu_stack(self, packed, source, guidance, chunk=None):
         """JBUStack.forward at inference: packed (featup.upsamplers.PackedStack: four parameter blocks, the final 1x1 convolution with

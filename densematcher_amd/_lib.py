@@ -116,6 +116,8 @@ SIGNATURES = {
     "dm_render_phong": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _d, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i]),
     "dm_jbu_filters_f32": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "dm_jbu_apply": (_i, [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _i, _p, _ll, _ll, _ll, _ll]),
+    "dm_jbu_apply_bwd_filters_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _ll, _ll, _ll, _ll, _p]),
+    "dm_jbu_apply_bwd_source_f32": (_i, [_p, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _p]),
     "dm_agg_gather_f32": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _d, _p, _i]),
     "dm_groupnorm_stats_f32": (_i, [_p, _i, _i, _i, _i, _p, _i, _p, _p]),
     "dm_groupnorm_relu_f32": (_i, [_p, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p, _p, _i]),

@@ -28,14 +28,10 @@
 // All memory operations are vector loads and stores.
 #include <math.h>
 
-#include <hip/hip_fp16.h>
-
-#include "dm_internal.h"
+#include "dm_jbu_common.h"
 
 namespace {
 constexpr int JB_KEY = 32;          // key_dim of JBULearnedRange
-constexpr int JB_T = 49;            // taps of the 7 x 7 kernel
-constexpr int JB_R = 3;             // radius
 // the packed parameter block of one stage, in floats (densematch.h)
 constexpr int PB_RP_W1 = 0, PB_RP_B1 = 96, PB_RP_W2 = 128, PB_RP_B2 = 1152, PB_FX_W1 = 1184, PB_FX_B1 = 3732, PB_FX_W2T = 3784,
               PB_FX_B2 = 6332, PB_SPATIAL = 6384, PB_TEMP = 6436, PB_SIZE = 6440;
@@ -46,16 +42,7 @@ constexpr int AP_PR = AP_TY + 2 * JB_R, AP_PC = AP_TX + 2 * JB_R;      // the pa
 constexpr int AP_SR = AP_TY / 2 + 8, AP_SC = AP_TX / 2 + 8;            // the source window: at most 16 x 24
 constexpr int AP_CB = 4;                                    // channels per pass
 
-// bicubic weights (A = -0.75) of the two phases of an exact 2x upsampling with align_corners=False: the source coordinate of output
-// u is u / 2 - 0.25; u odd: t = 0.25 on taps k-1 .. k+2 (k = u >> 1); u even: t = 0.75 on taps k-2 .. k+1.  All exact in binary.
-constexpr float BC_A = -0.10546875f, BC_B = 0.87890625f, BC_C = 0.26171875f, BC_D = -0.03515625f;
-
-__device__ __forceinline__ int jb_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * (n - 1) - i : i); }    // |i| excess < n
 __device__ __forceinline__ float jb_gelu(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-__device__ __forceinline__ float jb_load(const __half* p) { return __half2float(*p); }
-__device__ __forceinline__ float jb_load(const float* p) { return *p; }
-__device__ __forceinline__ void jb_store(float* p, float v) { *p = v; }
-__device__ __forceinline__ void jb_store(__half* p, float v) { *p = __float2half_rn(v); }
 
 // ---------------------------------------------------------------------------------------------------------------- keys
 // keys[b][p][:] = W2 gelu(W1 g + b1) + b2, g = guidance[b][:, p]
@@ -166,15 +153,6 @@ struct apply_args {
     const float* filt;
     void* out; long long ob, oc, oy, ox;
 };
-
-// the four source taps and weights of upsampled index u (0 <= u < 2 n), clamped to [0, n)
-__device__ __forceinline__ void jb_taps(int u, int n, int* tap, float* wt) {
-    const int k = u >> 1, first = (u & 1) ? k - 1 : k - 2;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) tap[q] = min(max(first + q, 0), n - 1);
-    if (u & 1) { wt[0] = BC_A; wt[1] = BC_B; wt[2] = BC_C; wt[3] = BC_D; }
-    else { wt[0] = BC_D; wt[1] = BC_C; wt[2] = BC_B; wt[3] = BC_A; }
-}
 
 template <typename TS, typename TO>
 __global__ void __launch_bounds__(256, 3) jbu_apply_kernel(apply_args a) {

@@ -59,17 +59,20 @@ def load_upsampler(path_or_state_dict, num_features):
     return upsampler.eval(), settings
 
 
-def upsample_features(upsampler, features_lr, image, use_unitnorm=False, use_channelnorm=False, route="auto", **kwargs):
+def upsample_features(upsampler, features_lr, image, use_unitnorm=False, use_channelnorm=False, route="auto", differentiable=False,
+                      **kwargs):
     """SDDINOFeatureExtractor.forward without the backbone (extractor.py:246-251): features_lr (B, C, h, w) from the 2D backbone, image
     (B, 3, H, W) the normalised image they were computed from -> features_hr (B, C, 16h, 16w).  route and kwargs (out_dtype=,
-    memory_format=, chunk=) go to JBUStack.forward; another upsampler (Bilinear) is called as the reference calls it."""
+    memory_format=, chunk=) go to JBUStack.forward, and so does differentiable (with route="device": record the autograd graph, so that
+    the upsampler can be trained or a loss on features_hr reach features_lr); another upsampler (Bilinear) is called as the reference
+    calls it."""
     num_features = features_lr.shape[1]
     if use_unitnorm:
         features_lr = UnitNorm(num_features)(features_lr)
     if use_channelnorm:
         features_lr = ChannelNorm(num_features)(features_lr)
     if hasattr(upsampler, "up1"):
-        return upsampler(features_lr, image, route=route, **kwargs)
+        return upsampler(features_lr, image, route=route, differentiable=differentiable, **kwargs)
     return upsampler(features_lr, image)
 
 

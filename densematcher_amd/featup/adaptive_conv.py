@@ -6,9 +6,10 @@ with input (B, C, H + I - 1, W + J - 1) already padded and filters (B, H, W, I, 
 Routes:
   torch    a loop over the I * J taps that accumulates shifted slices of the input in the reference kernel's order (i outer, j inner).
            No (I J) x C x H x W buffer is formed (unfold would form one), autograd records it, it runs on any device: the training path.
-  device   inference on dm_jbu_apply -- which fuses the bicubic upsampling and the padding into the convolution -- is reached through
-           JBULearnedRange / JBUStack; a bare padded input has no device kernel of its own, so here 'device' is refused and 'auto' is
-           the torch route.
+  device   dm_jbu_apply -- which fuses the bicubic upsampling and the padding into the convolution -- is reached through
+           JBULearnedRange / JBUStack: route='device' at inference, route='device', differentiable=True with its backward kernels
+           (featup.backward: dm_jbu_apply_bwd_filters_f32, dm_jbu_apply_bwd_source_f32).  A bare padded input has no device kernel of
+           its own, forward or backward, so here 'device' is refused and 'auto' is the torch route.
 """
 import torch
 
@@ -34,8 +35,9 @@ def adaptive_conv(input, filters, route="auto"):
     if input.shape[2] != filters.shape[1] + filters.shape[3] - 1 or input.shape[3] != filters.shape[2] + filters.shape[4] - 1:
         raise ValueError(f"adaptive_conv: input {tuple(input.shape)} is not filters {tuple(filters.shape)} padded by the kernel size - 1")
     if route == "device":
-        raise ValueError("adaptive_conv: the device kernel (dm_jbu_apply) upsamples and pads the source itself: use "
-                         "JBULearnedRange / JBUStack with route='device', or MatchEngine.jbu_apply")
+        raise ValueError("adaptive_conv: the device kernels (dm_jbu_apply and its backward) upsample and pad the source themselves: use "
+                         "JBULearnedRange / JBUStack with route='device' (differentiable=True where a gradient is needed), or "
+                         "MatchEngine.jbu_apply")
     return _tap_loop(input, filters)
 
 

@@ -12,6 +12,15 @@ Routes (forward(..., route=)):
            not exactly twice the source size (JBULearnedRange alone is more general than JBUStack ever uses; those cases stay on torch);
            RuntimeError without a GPU.
   auto     the device route where its conditions hold and tools/jbu_time.py measured it not slower (AUTO_DEVICE), else torch.
+
+forward(..., route="device", differentiable=True) is the device route that records the autograd graph (opt-in; 'torch' and 'auto' ignore
+the flag): the kernels of a stage come from the torch expressions (combined_kernel: autograd, training mode and Dropout2d as on the
+torch route), upsampling + padding + convolution run as ONE autograd node (featup.backward: dm_jbu_apply forward, dm_jbu_apply_bwd_*
+backward) that keeps the source and the kernels only, and JBUStack's final fixup_proj is the torch module.  In eval mode the node
+takes the kernels' VALUES from dm_jbu_filters_f32, so that a module's output has the bits of its inference device route whether or
+not a gradient is recorded (the gradient flows through the torch expressions; the two evaluations differ by fp32 rounding), and a
+call that records no graph is the inference route itself.  Conditions: source float16 | float32 and at least 2 x 2, guidance exactly
+twice the source, float32 parameters and guidance, everything on the GPU; anything else is refused by name.
 """
 import torch
 import torch.nn.functional as F
@@ -19,6 +28,7 @@ from torch import nn
 
 from .. import _routes
 from .adaptive_conv import adaptive_conv
+from .backward import jbu_apply
 
 # where tools/jbu_time.py measured the device route not slower than the torch route of the same process on an MI355X (README.md,
 # DESIGN.md section 4): "stack" = JBUStack, 17.9 ms against 155 ms (5 views, 768 channels, 24 x 24 -> 384 x 384, fp16 source);
@@ -44,6 +54,26 @@ def _route_of(module, route, source, guidance, kind, shape_obstacle):
     """what both modules hand to the one picker: "torch" or "device" for this call"""
     return _routes.pick_torch(route, type(module).__name__, lambda: _obstacle(module, source, guidance, shape_obstacle), AUTO_DEVICE[kind],
                               lambda: source.is_cuda and guidance.is_cuda and all(p.is_cuda for p in module.parameters()))
+
+
+def _diff_obstacle(module, source, guidance, shape_obstacle):
+    """why the differentiable device route cannot run this call, or None.  Training mode and tensors that require grad are none;
+    where the operands lie is asked only in a process that has a GPU (without one the answer is _routes.NO_GPU, as on the device route)"""
+    if shape_obstacle:
+        return shape_obstacle
+    if source.dtype not in (torch.float16, torch.float32):
+        return f"the source must be float16 or float32, not {source.dtype}"
+    if guidance.dtype != torch.float32 or any(p.dtype != torch.float32 for p in module.parameters()):
+        return "the guidance and the parameters must be float32 (the kernels of the adaptive convolution are)"
+    if _routes.engine_or_none() is not None and not (source.is_cuda and guidance.is_cuda and all(p.is_cuda for p in module.parameters())):
+        return "the source, the guidance and the parameters must be on the GPU"
+    return None
+
+
+def _differentiable_route(module, source, guidance, shape_obstacle):
+    """route='device', differentiable=True: passes, or raises as the one picker does"""
+    _routes.pick_torch("device", type(module).__name__ + " differentiable=True,", lambda: _diff_obstacle(module, source, guidance, shape_obstacle),
+                       True, lambda: True)
 
 
 class JBULearnedRange(nn.Module):
@@ -127,10 +157,24 @@ class JBULearnedRange(nn.Module):
             return "the source must be at least 2 x 2"
         return None
 
-    def forward(self, source, guidance, route="auto"):
-        """source (B, C, h, w), guidance (B, 3, H, W) -> (B, C, H, W)"""
+    def _forward_device_differentiable(self, source, guidance):
+        eng = _routes.engine_or_none()
+        B, _, H, W = guidance.shape
+        if self.training:
+            return jbu_apply(source, self.combined_kernel(guidance).reshape(B, H, W, self.diameter ** 2))
+        values = eng.jbu_filters(guidance, self.packed(eng.device))
+        if _routes.grad_obstacle([source, guidance] + list(self.parameters())) is None:
+            return eng.jbu_apply(source, values)                      # no graph to record: the inference route
+        return jbu_apply(source, self.combined_kernel(guidance).reshape(B, H, W, self.diameter ** 2), values)
+
+    def forward(self, source, guidance, route="auto", differentiable=False):
+        """source (B, C, h, w), guidance (B, 3, H, W) -> (B, C, H, W).  differentiable: with route="device", record the autograd graph
+        (module docstring); the other routes ignore it"""
         if source.shape[0] != guidance.shape[0]:
             raise ValueError("source and guidance differ in their batch size")
+        if differentiable and route == "device":
+            _differentiable_route(self, source, guidance, self._shape_obstacle(source, guidance))
+            return self._forward_device_differentiable(source, guidance)
         if _route_of(self, route, source, guidance, "stage", self._shape_obstacle(source, guidance)) == "torch":
             return self._forward_torch(source, guidance)
         eng = _routes.engine_or_none()
@@ -157,9 +201,9 @@ class JBUStack(nn.Module):
         self.fixup_proj = nn.Sequential(nn.Dropout2d(0.2), nn.Conv2d(feat_dim, feat_dim, kernel_size=1))
         self._packed = None
 
-    def upsample(self, source, guidance, up, route="torch"):
+    def upsample(self, source, guidance, up, route="torch", differentiable=False):
         h, w = source.shape[2:]
-        return up(source, F.adaptive_avg_pool2d(guidance, (2 * h, 2 * w)), route=route)
+        return up(source, F.adaptive_avg_pool2d(guidance, (2 * h, 2 * w)), route=route, differentiable=differentiable)
 
     def packed(self, device):
         conv = self.fixup_proj[1]
@@ -171,18 +215,23 @@ class JBUStack(nn.Module):
             self._packed = (stamp, w, b)
         return PackedStack([up.packed(device) for up in (self.up1, self.up2, self.up3, self.up4)], self._packed[1], self._packed[2])
 
-    def forward(self, source, guidance, route="auto", out_dtype=None, memory_format=None, chunk=None):
+    def forward(self, source, guidance, route="auto", out_dtype=None, memory_format=None, chunk=None, differentiable=False):
         """source (B, C, h, w) fp16 | fp32, guidance (B, 3, Hg, Wg) the image -> (B, C, 16 h, 16 w).
         Device route: fp32, NCHW-shaped with channels-last strides (the layout lifting reads fastest) unless out_dtype= / memory_format=
         (torch.contiguous_format | torch.channels_last) ask otherwise -- both convert with torch; chunk= bounds the views in flight
-        (at 384 x 384, C = 768 one view's fp32 output is 453 MB).  Torch route: the reference's result, converted likewise when asked."""
+        (at 384 x 384, C = 768 one view's fp32 output is 453 MB).  Torch route: the reference's result, converted likewise when asked.
+        differentiable: with route="device", record the autograd graph (module docstring): every stage on its differentiable device
+        route, the final fixup_proj on torch, fp32 NCHW, all views at once (chunk= is the inference route's); the other routes ignore it."""
         if source.shape[0] != guidance.shape[0]:
             raise ValueError("source and guidance differ in their batch size")
         shape_obstacle = None if min(source.shape[2:]) >= 2 else "the source must be at least 2 x 2"
-        if _route_of(self, route, source, guidance, "stack", shape_obstacle) == "torch":
+        recorded = differentiable and route == "device"
+        if recorded:
+            _differentiable_route(self, source, guidance, shape_obstacle)
+        if recorded or _route_of(self, route, source, guidance, "stack", shape_obstacle) == "torch":
             x = source
             for up in (self.up1, self.up2, self.up3, self.up4):
-                x = self.upsample(x, guidance, up, route="torch")
+                x = self.upsample(x, guidance, up, route="device" if recorded else "torch", differentiable=recorded)
             y = self.fixup_proj(x) * 0.1 + x
         else:
             eng = _routes.engine_or_none()

@@ -1054,6 +1054,35 @@ int dm_jbu_apply(dm_ctx* ctx, int B, int C, int h, int w, int src_dtype, const v
                  long long s_row, long long s_col, const float* filters, int out_dtype, void* out, long long o_view, long long o_chan,
                  long long o_row, long long o_col);
 
+/* ---- backward of dm_jbu_apply ------------------------------------------------------------
+ * The two gradients of out = filters * P, P = reflect_pad_3(bicubic_2x(src)) (reference third_party/featup/featup/adaptive_conv_cuda/
+ * adaptive_conv_kernel.cu: adaptive_conv_grad_filters_kernel, adaptive_conv_grad_input_kernel, and the backward of F.pad reflect and
+ * F.interpolate bicubic that autograd chains behind the latter), for B views.  Per axis P = A src with A of (2n + 6) x n: row p holds
+ * the four bicubic weights of upsampled index reflect(p - 3) on its clamped texels.  All arithmetic is fp32 fmaf; neither P nor its
+ * gradient is stored.  gout (B,C,2h,2w) fp32 is addressed through ELEMENT strides (view, channel, row, col) and only read: NCHW,
+ * channels-last, views of larger buffers and the all-zero strides of an expanded scalar are read where they lie.
+ *   dm_jbu_apply_bwd_filters_f32
+ *     gfilt[b,y,x,7i+j] = sum_c gout[b,c,y,x] * P[b,c,y+i,x+j], gfilt (B,2h,2w,49) fp32 dense, 16-byte aligned.  P has the bits
+ *     dm_jbu_apply computes; the sum is one fmaf chain over ascending c starting from zero.  Only where the output has fewer than 64
+ *     tiles of 16 x 32 pixels the channels are cut into n = min(ceil(C / 4), ceil(64 / tiles), 16) chunks of 4 ceil(ceil(C / 4) / n)
+ *     channels -- a function of (C, h, w) alone --, whose chains are added in ascending chunk order by a second launch; the partial
+ *     sums (n, B, 2h, 2w, 49) fp32 live in the workspace (at most 127 tiles' worth per chunk set: 12.7 MB per view).
+ *     src (B,C,h,w) fp16 | fp32 through element strides, as dm_jbu_apply reads it.
+ *   dm_jbu_apply_bwd_source_f32
+ *     gsrc = Ay^T gP Ax per (view, channel), gsrc (B,C,h,w) fp32 dense; gP[u,v] = sum_{i,j} gout[u-i,v-j] * filters[u-i,v-j,7i+j]
+ *     over the output pixels inside the image, an fmaf chain in the order i (outer), j (inner) starting from zero.  The transposes
+ *     are gathers in a fixed order: an upsampled index adds the padded indices that reflect onto it in ascending order, along y then
+ *     along x; a texel s adds the upsampled indices 2s-3 .. 2s+4 in ascending order (fmaf from zero), each with the sum of the weights
+ *     of its taps that clamp onto s, along x then along y.  filters (B,2h,2w,49) fp32 dense.  No workspace.
+ * No atomics, no sum whose order depends on scheduling; a view's bits depend on that view alone, whatever B.
+ * DM_EINVAL: h or w below 2 or above 8192, B or C not positive, B above 65535, a null operand, a dtype other than DM_F16 | DM_F32, a
+ * negative stride. */
+int dm_jbu_apply_bwd_filters_f32(dm_ctx* ctx, int B, int C, int h, int w, int src_dtype, const void* src, long long s_view,
+                                 long long s_chan, long long s_row, long long s_col, const float* gout, long long g_view,
+                                 long long g_chan, long long g_row, long long g_col, float* gfilt);
+int dm_jbu_apply_bwd_source_f32(dm_ctx* ctx, int B, int C, int h, int w, const float* gout, long long g_view, long long g_chan,
+                                long long g_row, long long g_col, const float* filters, float* gsrc);
+
 /* ---- aggregation network of the 2D backbone --------------------------------------------
  * The part of the reference between the raw outputs of the frozen backbones and features_lr (densematcher/featurizers/SDDINO.py:53-57,
  * 67-90; modules/projection_network.py:89-123; modules/resnet.py:271-287), inference.  Everything fp32 on rows = pixels, channels
