@@ -140,7 +140,8 @@ class _DiffusionNetOps:
                           "evecs": Phi[q, :n] if k_eig > 0 else torch.zeros((n, 0), dtype=torch.float64, device=self.device)}
         return res
 
-    # ------------------------------------------------------------- DiffusionNet forward (dm_dnet_*_f32)
+    # ------------------------------------------------------------- DiffusionNet layers: what the fp32 and the fp16 family share
+    # (`who` is the public method an error message names; `half` picks the dm_dnet_*_f16 family)
     def _dnet_counts(self, n_verts, Bn):
         if n_verts is None:
             return None
@@ -159,37 +160,169 @@ class _DiffusionNetOps:
             raise ValueError(f"{name}: out must have adjacent elements in a row and evenly spaced rows")
         return out, ld
 
-    def dnet_linear(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None):
-        """out[b,i,:] = act(concat(srcs)[b,i,:] weight^T + bias) + resid[b,i,:] (dm_dnet_linear_f32): srcs one tensor or up to three
-        (B, N, w_s) (or all (N, w_s)), weight (C_out, sum w_s) as nn.Linear stores it; the concatenation is never formed.  n_verts
-        (B) int32: rows behind a mesh's count are not read and come out as zeros."""
+    def _dnet_ws(self, nbytes):
+        return torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=self.device)
+
+    def _dnet_ell_rows(self, who, Bn, N, rows, t=""):
+        """(row_len, cols, gx, gy) of the gradient operators (t = "_t": of their transposes) on the device, held to (B,N) and (B,N,nnz)"""
+        row_len, cols = self._dev(rows[0], torch.int32, "row_len" + t), self._dev(rows[1], torch.int32, "cols" + t)
+        gx, gy = self._dev(rows[2], torch.float32, "gx" + t), self._dev(rows[3], torch.float32, "gy" + t)
+        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
+            raise ValueError(f"{who}: row_len{t} (B,N), cols{t} / gx{t} / gy{t} (B,N,nnz{t})")
+        return row_len, cols, gx, gy
+
+    def _dnet_matrices(self, who, A_re, A_im, dtype, Cw):
+        """A_re and A_im (or None) as (C, C) operands that share one leading dimension: (A_re, A_im, lda)"""
+        Are, lda = self._strided(A_re, dtype, "A_re")
+        Aim = None
+        if A_im is not None:
+            Aim, lda2 = self._strided(A_im, dtype, "A_im")
+            if lda2 != lda:
+                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
+        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
+            raise ValueError(f"{who}: A_re / A_im must be (C, C)")
+        return Are, Aim, lda
+
+    @staticmethod
+    def _dnet_src_args(mats, half):
+        """the (pointer, width, ld[, dtype flag]) argument groups of up to three sources, absent ones null"""
+        a = [(_ptr(m), m.shape[2], ld) + ((_flag(m),) if half else ()) for m, ld in mats]
+        return a + [(_ptr(None), 0, 0) + ((_lib.DM_F32,) if half else ())] * (3 - len(a))
+
+    def _dnet_linear_operands(self, who, half, srcs, weight, bias, resid):
+        """The operands of a linear layer, checked against each other.  fp16 family: a source or a bias keeps its dtype when that is
+        float16 or float32, the weight is float16.  Returns (flat, mats, W, ldw, bias, R, ldr)."""
         srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
         if not 1 <= len(srcs) <= 3:
-            raise ValueError("dnet_linear: one to three sources")
+            raise ValueError(f"{who}: one to three sources")
         flat = srcs[0].dim() == 2
         if flat:
             srcs = [s.unsqueeze(0) for s in srcs]
             resid = None if resid is None else resid.unsqueeze(0)
-        mats = [self._strided(s, torch.float32, "src") for s in srcs]
+        mats = [self._strided(s, _kept(s) if half else torch.float32, "src") for s in srcs]
         Bn, N = mats[0][0].shape[:2]
         if any(m.shape[:2] != (Bn, N) for m, _ in mats):
-            raise ValueError("dnet_linear: the sources differ in their leading dimensions")
-        W, ldw = self._strided(weight, torch.float32, "weight")
+            raise ValueError(f"{who}: the sources differ in their leading dimensions")
+        W, ldw = self._strided(weight, torch.float16 if half else torch.float32, "weight")
         if W.dim() != 2 or W.shape[1] != sum(m.shape[2] for m, _ in mats):
-            raise ValueError(f"dnet_linear: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
-        C_out = W.shape[0]
-        bias = None if bias is None else self._dev(bias, torch.float32, "bias")
-        if bias is not None and bias.shape != (C_out,):
-            raise ValueError("dnet_linear: bias must be (C_out,)")
+            raise ValueError(f"{who}: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
+        bias = None if bias is None else self._dev(bias, _kept(bias) if half else torch.float32, "bias")
+        if bias is not None and bias.shape != (W.shape[0],):
+            raise ValueError(f"{who}: bias must be (C_out,)")
         R, ldr = (None, 0) if resid is None else self._strided(resid, torch.float32, "resid")
-        if R is not None and tuple(R.shape) != (Bn, N, C_out):
-            raise ValueError("dnet_linear: resid must have the shape of the output")
+        if R is not None and tuple(R.shape) != (Bn, N, W.shape[0]):
+            raise ValueError(f"{who}: resid must have the shape of the output")
+        return flat, mats, W, ldw, bias, R, ldr
+
+    def _dnet_gradient_features(self, who, half, x, row_len, cols, gx, gy, A_re, A_im, n_verts, out):
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        row_len, cols, gx, gy = self._dnet_ell_rows(who, Bn, N, (row_len, cols, gx, gy))
+        Are, Aim, lda = self._dnet_matrices(who, A_re, A_im, torch.float16 if half else torch.float32, Cw)
+        nv = self._dnet_counts(n_verts, Bn)
+        out, ldo = self._dnet_out(out, Bn, N, Cw, who)
+        fn = self.lib.dm_dnet_gradfeat_f16 if half else self.lib.dm_dnet_gradfeat_f32
+        self._chk(fn(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
+                     _ptr(out), ldo))
+        return out
+
+    def _dnet_linear_backward(self, who, half, grad_out, srcs, weight, y, n_verts, need_src, need_weight, need_bias, out):
+        lib, sfx = self.lib, "_f16" if half else "_f32"
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        flat = G.dim() == 2
+        if flat:
+            G = G.unsqueeze(0)
+        Bn, N, C_out = G.shape
+        srcs = [srcs] if isinstance(srcs, (torch.Tensor, int)) else list(srcs)
+        if not 1 <= len(srcs) <= 3:
+            raise ValueError(f"{who}: one to three sources")
+        widths = [int(s) if isinstance(s, int) else int(s.shape[-1]) for s in srcs]
+        need_src = [bool(need_src)] * len(srcs) if isinstance(need_src, bool) else [bool(f) for f in need_src]
+        if len(need_src) != len(srcs):
+            raise ValueError(f"{who}: need_src has one flag per source")
+        W, ldw = (None, 0)
+        if any(need_src):
+            if weight is None:
+                raise ValueError(f"{who}: the gradient of a source reads the weight")
+            W, ldw = self._strided(weight, torch.float16 if half else torch.float32, "weight")
+            if W.dim() != 2 or tuple(W.shape) != (C_out, sum(widths)):
+                raise ValueError(f"{who}: weight {tuple(W.shape)} does not match grad_out ({C_out}) and the summed source widths {sum(widths)}")
+        Y, ldy = (None, 0)
+        if y is not None:
+            Y, ldy = self._strided(y.unsqueeze(0) if flat else y, torch.float32, "y")
+            if tuple(Y.shape) != (Bn, N, C_out):
+                raise ValueError(f"{who}: y must have the shape of grad_out")
+        nv = self._dnet_counts(n_verts, Bn)
+        act = 0 if Y is None else 1
+        d_src = [None] * len(srcs)
+        if any(need_src):
+            outs = [None] * len(srcs) if out is None else list(out)
+            a = []
+            for s, (w, need) in enumerate(zip(widths, need_src)):
+                if need:
+                    d_src[s], ld = self._dnet_out(None if outs[s] is None else (outs[s].unsqueeze(0) if flat else outs[s]), Bn, N, w, who)
+                    a.append((d_src[s], w, ld))
+                else:
+                    a.append((None, w, w))
+            a += [(None, 0, 0)] * (3 - len(a))
+            self._chk(getattr(lib, "dm_dnet_linear_bwd_data" + sfx)(self.ctx, Bn, N, C_out, len(srcs), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(W), ldw,
+                                                                    _ptr(nv), _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2],
+                                                                    _ptr(a[2][0]), a[2][1], a[2][2]))
+        dW = db = None
+        if need_weight or need_bias:
+            if any(isinstance(s, int) for s in srcs):
+                raise ValueError(f"{who}: the weight and bias gradients read the sources")
+            mats = [self._strided(s.unsqueeze(0) if flat else s, _kept(s) if half else torch.float32, "src") for s in srcs]
+            if any(tuple(m.shape[:2]) != (Bn, N) for m, _ in mats):
+                raise ValueError(f"{who}: the sources differ from grad_out in their leading dimensions")
+            a = self._dnet_src_args(mats, half)
+            dW = torch.empty((C_out, sum(widths)), dtype=torch.float32, device=self.device) if need_weight else None
+            db = torch.empty((C_out,), dtype=torch.float32, device=self.device) if need_bias else None
+            ws = self._dnet_ws((lib.dm_dnet_linear_bwd_f16_bytes if half else lib.dm_dnet_linear_bwd_bytes)(Bn, C_out, sum(widths)))
+            self._chk(getattr(lib, "dm_dnet_linear_bwd_weight" + sfx)(self.ctx, Bn, N, C_out, len(mats), _ptr(G), ldg, _ptr(Y), ldy, act, *a[0], *a[1], *a[2],
+                                                                      _ptr(nv), _ptr(ws), _ptr(dW), sum(widths), _ptr(db)))
+        if flat:
+            d_src = [None if d is None else d[0] for d in d_src]
+        return d_src, dW, db
+
+    def _dnet_gradient_features_backward(self, who, half, grad_out, x, row_len, cols, gx, gy, rows_t, A_re, A_im, n_verts, need_x, need_A, out):
+        lib = self.lib
+        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
+        X, ldx = self._strided(x, torch.float32, "x")
+        Bn, N, Cw = X.shape
+        if tuple(G.shape) != (Bn, N, Cw):
+            raise ValueError(f"{who}: grad_out must have the shape of x")
+        row_len, cols, gx, gy = self._dnet_ell_rows(who, Bn, N, (row_len, cols, gx, gy))
+        rl_t = cols_t = gx_t = gy_t = None
+        nnz_t = 0
+        if need_x:
+            if rows_t is None:
+                raise ValueError(f"{who}: the gradient of x reads the transposed rows")
+            rl_t, cols_t, gx_t, gy_t = self._dnet_ell_rows(who, Bn, N, rows_t, "_t")
+            nnz_t = cols_t.shape[2]
+        Are, Aim, lda = self._dnet_matrices(who, A_re, A_im, torch.float16 if half else torch.float32, Cw)
+        nv = self._dnet_counts(n_verts, Bn)
+        dx, lddx = self._dnet_out(out, Bn, N, Cw, who) if need_x else (None, 0)
+        dAre = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A else None
+        dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
+        ws = self._dnet_ws((lib.dm_dnet_gradfeat_bwd_f16_bytes if half else lib.dm_dnet_gradfeat_bwd_bytes)(Bn, N, Cw))
+        fn = lib.dm_dnet_gradfeat_bwd_f16 if half else lib.dm_dnet_gradfeat_bwd_f32
+        self._chk(fn(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t), _ptr(cols_t), _ptr(gx_t),
+                     _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
+        return dx, dAre, dAim
+
+    # ------------------------------------------------------------- DiffusionNet forward (dm_dnet_*_f32)
+    def dnet_linear(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None):
+        """out[b,i,:] = act(concat(srcs)[b,i,:] weight^T + bias) + resid[b,i,:] (dm_dnet_linear_f32): srcs one tensor or up to three
+        (B, N, w_s) (or all (N, w_s)), weight (C_out, sum w_s) as nn.Linear stores it; the concatenation is never formed.  n_verts
+        (B) int32: rows behind a mesh's count are not read and come out as zeros."""
+        flat, mats, W, ldw, bias, R, ldr = self._dnet_linear_operands("dnet_linear", False, srcs, weight, bias, resid)
+        (Bn, N), C_out = mats[0][0].shape[:2], W.shape[0]
         nv = self._dnet_counts(n_verts, Bn)
         out, ldo = self._dnet_out(out, Bn, N, C_out, "dnet_linear")
-        a = [(m, m.shape[2], ld) for m, ld in mats] + [(None, 0, 0)] * (3 - len(mats))
-        self._chk(self.lib.dm_dnet_linear_f32(self.ctx, Bn, N, C_out, len(mats), _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2],
-                                              _ptr(a[2][0]), a[2][1], a[2][2], _ptr(W), ldw, _ptr(bias), _ptr(R), ldr, 1 if relu else 0, _ptr(nv),
-                                              _ptr(out), ldo))
+        a = self._dnet_src_args(mats, False)
+        self._chk(self.lib.dm_dnet_linear_f32(self.ctx, Bn, N, C_out, len(mats), *a[0], *a[1], *a[2], _ptr(W), ldw, _ptr(bias), _ptr(R), ldr,
+                                              1 if relu else 0, _ptr(nv), _ptr(out), ldo))
         return out[0] if flat else out
 
     def dnet_diffuse(self, x, mass, evals, evecs, times, n_verts=None, out=None):
@@ -213,32 +346,9 @@ class _DiffusionNetOps:
     def dnet_gradient_features(self, x, row_len, cols, gx, gy, A_re, A_im=None, n_verts=None, out=None):
         """tanh(gX * B_re + gY * B_im) of SpatialGradientFeatures (dm_dnet_gradfeat_f32) from the ELL rows of the gradient operators
         (row_len (B,N) int32; cols int32, gx, gy float32 (B,N,nnz)) and x (B,N,C); A_im None: one matrix, no rotation."""
-        X, ldx = self._strided(x, torch.float32, "x")
-        Bn, N, Cw = X.shape
-        row_len = self._dev(row_len, torch.int32, "row_len")
-        cols = self._dev(cols, torch.int32, "cols")
-        gx = self._dev(gx, torch.float32, "gx")
-        gy = self._dev(gy, torch.float32, "gy")
-        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
-            raise ValueError("dnet_gradient_features: row_len (B,N), cols / gx / gy (B,N,nnz)")
-        Are, lda = self._strided(A_re, torch.float32, "A_re")
-        Aim = None
-        if A_im is not None:
-            Aim, lda2 = self._strided(A_im, torch.float32, "A_im")
-            if lda2 != lda:
-                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
-        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
-            raise ValueError("dnet_gradient_features: A_re / A_im must be (C, C)")
-        nv = self._dnet_counts(n_verts, Bn)
-        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features")
-        self._chk(self.lib.dm_dnet_gradfeat_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
-                                                _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
-        return out
+        return self._dnet_gradient_features("dnet_gradient_features", False, x, row_len, cols, gx, gy, A_re, A_im, n_verts, out)
 
     # ------------------------------------------------------------- DiffusionNet backward (dm_dnet_*_bwd_f32)
-    def _dnet_ws(self, nbytes):
-        return torch.empty(max(int(nbytes), 4), dtype=torch.uint8, device=self.device)
-
     def dnet_linear_backward(self, grad_out, srcs, weight, y=None, n_verts=None, need_src=True, need_weight=True, need_bias=True, out=None):
         """The gradients of dnet_linear (dm_dnet_linear_bwd_data_f32, dm_dnet_linear_bwd_weight_f32).  grad_out (B, N, C_out); srcs the
         forward's sources; weight (C_out, sum w_s); y: the saved output of a relu=True call made WITHOUT resid (its mask y > 0 is
@@ -246,63 +356,7 @@ class _DiffusionNetOps:
         out: a list with a (B, N, w_s) tensor or None per source.  Only the weight and bias gradients read the sources: without
         them a source may be given as its width (an int).
         Returns (list of source gradients or None each, grad_weight or None, grad_bias or None)."""
-        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
-        flat = G.dim() == 2
-        if flat:
-            G = G.unsqueeze(0)
-        Bn, N, C_out = G.shape
-        srcs = [srcs] if isinstance(srcs, (torch.Tensor, int)) else list(srcs)
-        if not 1 <= len(srcs) <= 3:
-            raise ValueError("dnet_linear_backward: one to three sources")
-        widths = [int(s) if isinstance(s, int) else int(s.shape[-1]) for s in srcs]
-        need_src = [bool(need_src)] * len(srcs) if isinstance(need_src, bool) else [bool(f) for f in need_src]
-        if len(need_src) != len(srcs):
-            raise ValueError("dnet_linear_backward: need_src has one flag per source")
-        W, ldw = (None, 0)
-        if any(need_src):
-            if weight is None:
-                raise ValueError("dnet_linear_backward: the gradient of a source reads the weight")
-            W, ldw = self._strided(weight, torch.float32, "weight")
-            if W.dim() != 2 or tuple(W.shape) != (C_out, sum(widths)):
-                raise ValueError(f"dnet_linear_backward: weight {tuple(W.shape)} does not match grad_out ({C_out}) and the summed source widths {sum(widths)}")
-        Y, ldy = (None, 0)
-        if y is not None:
-            Y, ldy = self._strided(y.unsqueeze(0) if flat else y, torch.float32, "y")
-            if tuple(Y.shape) != (Bn, N, C_out):
-                raise ValueError("dnet_linear_backward: y must have the shape of grad_out")
-        nv = self._dnet_counts(n_verts, Bn)
-        act = 0 if Y is None else 1
-        d_src = [None] * len(srcs)
-        if any(need_src):
-            outs = [None] * len(srcs) if out is None else list(out)
-            a = []
-            for s, (w, need) in enumerate(zip(widths, need_src)):
-                if need:
-                    d_src[s], ld = self._dnet_out(None if outs[s] is None else (outs[s].unsqueeze(0) if flat else outs[s]), Bn, N, w,
-                                                  "dnet_linear_backward")
-                    a.append((d_src[s], w, ld))
-                else:
-                    a.append((None, w, w))
-            a += [(None, 0, 0)] * (3 - len(a))
-            self._chk(self.lib.dm_dnet_linear_bwd_data_f32(self.ctx, Bn, N, C_out, len(srcs), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(W), ldw, _ptr(nv),
-                                                           _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2]))
-        dW = db = None
-        if need_weight or need_bias:
-            if any(isinstance(s, int) for s in srcs):
-                raise ValueError("dnet_linear_backward: the weight and bias gradients read the sources")
-            mats = [self._strided(s.unsqueeze(0) if flat else s, torch.float32, "src") for s in srcs]
-            if any(tuple(m.shape[:2]) != (Bn, N) for m, _ in mats):
-                raise ValueError("dnet_linear_backward: the sources differ from grad_out in their leading dimensions")
-            a = [(m, m.shape[2], ld) for m, ld in mats] + [(None, 0, 0)] * (3 - len(mats))
-            dW = torch.empty((C_out, sum(widths)), dtype=torch.float32, device=self.device) if need_weight else None
-            db = torch.empty((C_out,), dtype=torch.float32, device=self.device) if need_bias else None
-            ws = self._dnet_ws(self.lib.dm_dnet_linear_bwd_bytes(Bn, C_out, sum(widths)))
-            self._chk(self.lib.dm_dnet_linear_bwd_weight_f32(self.ctx, Bn, N, C_out, len(mats), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(a[0][0]), a[0][1],
-                                                             a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2], _ptr(nv), _ptr(ws),
-                                                             _ptr(dW), sum(widths), _ptr(db)))
-        if flat:
-            d_src = [None if d is None else d[0] for d in d_src]
-        return d_src, dW, db
+        return self._dnet_linear_backward("dnet_linear_backward", False, grad_out, srcs, weight, y, n_verts, need_src, need_weight, need_bias, out)
 
     def dnet_diffuse_backward(self, grad_out, x, mass, evals, evecs, times, n_verts=None, need_x=True, need_times=True, out=None):
         """The gradients of dnet_diffuse (dm_dnet_diffuse_bwd_f32) with respect to x and to the clamped times: grad_out, x (B,N,C) (x
@@ -334,45 +388,8 @@ class _DiffusionNetOps:
         """The gradients of dnet_gradient_features (dm_dnet_gradfeat_bwd_f32): grad_out and the saved x (B,N,C), the forward's rows,
         rows_t = (row_len_t, cols_t, gx_t, gy_t), the rows of the transposed operators (PackedOperators.transposed_rows(); None with
         need_x=False).  Returns (grad_x or None, grad_A_re or None, grad_A_im or None)."""
-        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
-        X, ldx = self._strided(x, torch.float32, "x")
-        Bn, N, Cw = X.shape
-        if tuple(G.shape) != (Bn, N, Cw):
-            raise ValueError("dnet_gradient_features_backward: grad_out must have the shape of x")
-        row_len = self._dev(row_len, torch.int32, "row_len")
-        cols = self._dev(cols, torch.int32, "cols")
-        gx = self._dev(gx, torch.float32, "gx")
-        gy = self._dev(gy, torch.float32, "gy")
-        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
-            raise ValueError("dnet_gradient_features_backward: row_len (B,N), cols / gx / gy (B,N,nnz)")
-        rl_t = cols_t = gx_t = gy_t = None
-        nnz_t = 0
-        if need_x:
-            if rows_t is None:
-                raise ValueError("dnet_gradient_features_backward: the gradient of x reads the transposed rows")
-            rl_t, cols_t = self._dev(rows_t[0], torch.int32, "row_len_t"), self._dev(rows_t[1], torch.int32, "cols_t")
-            gx_t, gy_t = self._dev(rows_t[2], torch.float32, "gx_t"), self._dev(rows_t[3], torch.float32, "gy_t")
-            if (cols_t.dim() != 3 or tuple(cols_t.shape[:2]) != (Bn, N) or gx_t.shape != cols_t.shape or gy_t.shape != cols_t.shape
-                    or tuple(rl_t.shape) != (Bn, N)):
-                raise ValueError("dnet_gradient_features_backward: row_len_t (B,N), cols_t / gx_t / gy_t (B,N,nnz_t)")
-            nnz_t = cols_t.shape[2]
-        Are, lda = self._strided(A_re, torch.float32, "A_re")
-        Aim = None
-        if A_im is not None:
-            Aim, lda2 = self._strided(A_im, torch.float32, "A_im")
-            if lda2 != lda:
-                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
-        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
-            raise ValueError("dnet_gradient_features_backward: A_re / A_im must be (C, C)")
-        nv = self._dnet_counts(n_verts, Bn)
-        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_backward") if need_x else (None, 0)
-        dAre = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A else None
-        dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
-        ws = self._dnet_ws(self.lib.dm_dnet_gradfeat_bwd_bytes(Bn, N, Cw))
-        self._chk(self.lib.dm_dnet_gradfeat_bwd_f32(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t),
-                                                    _ptr(cols_t), _ptr(gx_t), _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
-                                                    _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
-        return dx, dAre, dAim
+        return self._dnet_gradient_features_backward("dnet_gradient_features_backward", False, grad_out, x, row_len, cols, gx, gy, rows_t, A_re, A_im,
+                                                     n_verts, need_x, need_A, out)
 
     # ------------------------------------------------------------- DiffusionNet backward, fp16 operands (dm_dnet_*_bwd_f16)
     def dnet_linear_backward_f16(self, grad_out, srcs, weight_h, y=None, n_verts=None, need_src=True, need_weight=True, need_bias=True, out=None):
@@ -380,63 +397,7 @@ class _DiffusionNetOps:
         weight_h (C_out, sum w_s) float16, the rounded matrix the forward multiplied; every source float16 or float32 in its own dtype
         (float32 elements are rounded as they are staged).  The gradients are float32; grad_weight belongs to the float32 master of
         weight_h.  Arguments and the returned triple as dnet_linear_backward."""
-        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
-        flat = G.dim() == 2
-        if flat:
-            G = G.unsqueeze(0)
-        Bn, N, C_out = G.shape
-        srcs = [srcs] if isinstance(srcs, (torch.Tensor, int)) else list(srcs)
-        if not 1 <= len(srcs) <= 3:
-            raise ValueError("dnet_linear_backward_f16: one to three sources")
-        widths = [int(s) if isinstance(s, int) else int(s.shape[-1]) for s in srcs]
-        need_src = [bool(need_src)] * len(srcs) if isinstance(need_src, bool) else [bool(f) for f in need_src]
-        if len(need_src) != len(srcs):
-            raise ValueError("dnet_linear_backward_f16: need_src has one flag per source")
-        W, ldw = (None, 0)
-        if any(need_src):
-            if weight_h is None:
-                raise ValueError("dnet_linear_backward_f16: the gradient of a source reads the weight")
-            W, ldw = self._strided(weight_h, torch.float16, "weight")
-            if W.dim() != 2 or tuple(W.shape) != (C_out, sum(widths)):
-                raise ValueError(f"dnet_linear_backward_f16: weight {tuple(W.shape)} does not match grad_out ({C_out}) and the summed source widths {sum(widths)}")
-        Y, ldy = (None, 0)
-        if y is not None:
-            Y, ldy = self._strided(y.unsqueeze(0) if flat else y, torch.float32, "y")
-            if tuple(Y.shape) != (Bn, N, C_out):
-                raise ValueError("dnet_linear_backward_f16: y must have the shape of grad_out")
-        nv = self._dnet_counts(n_verts, Bn)
-        act = 0 if Y is None else 1
-        d_src = [None] * len(srcs)
-        if any(need_src):
-            outs = [None] * len(srcs) if out is None else list(out)
-            a = []
-            for s, (w, need) in enumerate(zip(widths, need_src)):
-                if need:
-                    d_src[s], ld = self._dnet_out(None if outs[s] is None else (outs[s].unsqueeze(0) if flat else outs[s]), Bn, N, w,
-                                                  "dnet_linear_backward_f16")
-                    a.append((d_src[s], w, ld))
-                else:
-                    a.append((None, w, w))
-            a += [(None, 0, 0)] * (3 - len(a))
-            self._chk(self.lib.dm_dnet_linear_bwd_data_f16(self.ctx, Bn, N, C_out, len(srcs), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(W), ldw, _ptr(nv),
-                                                           _ptr(a[0][0]), a[0][1], a[0][2], _ptr(a[1][0]), a[1][1], a[1][2], _ptr(a[2][0]), a[2][1], a[2][2]))
-        dW = db = None
-        if need_weight or need_bias:
-            if any(isinstance(s, int) for s in srcs):
-                raise ValueError("dnet_linear_backward_f16: the weight and bias gradients read the sources")
-            mats = [self._strided(s.unsqueeze(0) if flat else s, _kept(s), "src") for s in srcs]
-            if any(tuple(m.shape[:2]) != (Bn, N) for m, _ in mats):
-                raise ValueError("dnet_linear_backward_f16: the sources differ from grad_out in their leading dimensions")
-            a = [(m, m.shape[2], ld, _flag(m)) for m, ld in mats] + [(None, 0, 0, _lib.DM_F32)] * (3 - len(mats))
-            dW = torch.empty((C_out, sum(widths)), dtype=torch.float32, device=self.device) if need_weight else None
-            db = torch.empty((C_out,), dtype=torch.float32, device=self.device) if need_bias else None
-            ws = self._dnet_ws(self.lib.dm_dnet_linear_bwd_f16_bytes(Bn, C_out, sum(widths)))
-            self._chk(self.lib.dm_dnet_linear_bwd_weight_f16(self.ctx, Bn, N, C_out, len(mats), _ptr(G), ldg, _ptr(Y), ldy, act, _ptr(a[0][0]), *a[0][1:],
-                                                             _ptr(a[1][0]), *a[1][1:], _ptr(a[2][0]), *a[2][1:], _ptr(nv), _ptr(ws), _ptr(dW), sum(widths),
-                                                             _ptr(db)))
-        if flat:
-            d_src = [None if d is None else d[0] for d in d_src]
-        return d_src, dW, db
+        return self._dnet_linear_backward("dnet_linear_backward_f16", True, grad_out, srcs, weight_h, y, n_verts, need_src, need_weight, need_bias, out)
 
     def dnet_diffuse_backward_f16(self, grad_out, x, evecs_h, mevecs_h, e1, e2, evals, times, n_verts=None, need_x=True, need_times=True, out=None):
         """The gradients of dnet_diffuse_f16 (dm_dnet_diffuse_bwd_f16) with respect to x and to the clamped times: grad_out, x (B,N,C)
@@ -471,81 +432,25 @@ class _DiffusionNetOps:
         """The gradients of dnet_gradient_features_f16 (dm_dnet_gradfeat_bwd_f16): A_re_h / A_im_h float16, the rounded matrices the forward
         multiplied; everything else as dnet_gradient_features_backward.  Returns (grad_x or None, grad_A_re or None, grad_A_im or None),
         float32; the matrix gradients belong to the float32 masters."""
-        G, ldg = self._strided(grad_out, torch.float32, "grad_out")
-        X, ldx = self._strided(x, torch.float32, "x")
-        Bn, N, Cw = X.shape
-        if tuple(G.shape) != (Bn, N, Cw):
-            raise ValueError("dnet_gradient_features_backward_f16: grad_out must have the shape of x")
-        row_len = self._dev(row_len, torch.int32, "row_len")
-        cols = self._dev(cols, torch.int32, "cols")
-        gx = self._dev(gx, torch.float32, "gx")
-        gy = self._dev(gy, torch.float32, "gy")
-        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
-            raise ValueError("dnet_gradient_features_backward_f16: row_len (B,N), cols / gx / gy (B,N,nnz)")
-        rl_t = cols_t = gx_t = gy_t = None
-        nnz_t = 0
-        if need_x:
-            if rows_t is None:
-                raise ValueError("dnet_gradient_features_backward_f16: the gradient of x reads the transposed rows")
-            rl_t, cols_t = self._dev(rows_t[0], torch.int32, "row_len_t"), self._dev(rows_t[1], torch.int32, "cols_t")
-            gx_t, gy_t = self._dev(rows_t[2], torch.float32, "gx_t"), self._dev(rows_t[3], torch.float32, "gy_t")
-            if (cols_t.dim() != 3 or tuple(cols_t.shape[:2]) != (Bn, N) or gx_t.shape != cols_t.shape or gy_t.shape != cols_t.shape
-                    or tuple(rl_t.shape) != (Bn, N)):
-                raise ValueError("dnet_gradient_features_backward_f16: row_len_t (B,N), cols_t / gx_t / gy_t (B,N,nnz_t)")
-            nnz_t = cols_t.shape[2]
-        Are, lda = self._strided(A_re_h, torch.float16, "A_re")
-        Aim = None
-        if A_im_h is not None:
-            Aim, lda2 = self._strided(A_im_h, torch.float16, "A_im")
-            if lda2 != lda:
-                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
-        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
-            raise ValueError("dnet_gradient_features_backward_f16: A_re / A_im must be (C, C)")
-        nv = self._dnet_counts(n_verts, Bn)
-        dx, lddx = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_backward_f16") if need_x else (None, 0)
-        dAre = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A else None
-        dAim = torch.empty((Cw, Cw), dtype=torch.float32, device=self.device) if need_A and Aim is not None else None
-        ws = self._dnet_ws(self.lib.dm_dnet_gradfeat_bwd_f16_bytes(Bn, N, Cw))
-        self._chk(self.lib.dm_dnet_gradfeat_bwd_f16(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), nnz_t, _ptr(rl_t),
-                                                    _ptr(cols_t), _ptr(gx_t), _ptr(gy_t), _ptr(G), ldg, _ptr(X), ldx, _ptr(Are), _ptr(Aim), lda, _ptr(nv),
-                                                    _ptr(ws), _ptr(dx), lddx, _ptr(dAre), _ptr(dAim), Cw))
-        return dx, dAre, dAim
+        return self._dnet_gradient_features_backward("dnet_gradient_features_backward_f16", True, grad_out, x, row_len, cols, gx, gy, rows_t, A_re_h,
+                                                     A_im_h, n_verts, need_x, need_A, out)
 
     # ------------------------------------------------------------- DiffusionNet forward, fp16 operands (dm_dnet_*_f16)
     def dnet_linear_f16(self, srcs, weight, bias=None, resid=None, relu=False, n_verts=None, out=None, out_dtype=torch.float32):
         """dnet_linear on fp16 operands (dm_dnet_linear_f16): every source float16 or float32 in its own dtype (float32 elements are
         rounded as they are staged), weight (C_out, sum w_s) float16 read where it lies, bias float16 or float32, resid float32;
         fp32 accumulation, + bias, act, + resid; out float32 or float16 (out_dtype, or the dtype of out)."""
-        srcs = [srcs] if isinstance(srcs, torch.Tensor) else list(srcs)
-        if not 1 <= len(srcs) <= 3:
-            raise ValueError("dnet_linear_f16: one to three sources")
-        flat = srcs[0].dim() == 2
-        if flat:
-            srcs = [s.unsqueeze(0) for s in srcs]
-            resid = None if resid is None else resid.unsqueeze(0)
-        mats = [self._strided(s, _kept(s), "src") for s in srcs]
-        Bn, N = mats[0][0].shape[:2]
-        if any(m.shape[:2] != (Bn, N) for m, _ in mats):
-            raise ValueError("dnet_linear_f16: the sources differ in their leading dimensions")
-        W, ldw = self._strided(weight, torch.float16, "weight")
-        if W.dim() != 2 or W.shape[1] != sum(m.shape[2] for m, _ in mats):
-            raise ValueError(f"dnet_linear_f16: weight {tuple(W.shape)} does not match the summed source widths {sum(m.shape[2] for m, _ in mats)}")
-        C_out = W.shape[0]
-        bias = None if bias is None else self._dev(bias, _kept(bias), "bias")
-        if bias is not None and bias.shape != (C_out,):
-            raise ValueError("dnet_linear_f16: bias must be (C_out,)")
-        R, ldr = (None, 0) if resid is None else self._strided(resid, torch.float32, "resid")
-        if R is not None and tuple(R.shape) != (Bn, N, C_out):
-            raise ValueError("dnet_linear_f16: resid must have the shape of the output")
+        flat, mats, W, ldw, bias, R, ldr = self._dnet_linear_operands("dnet_linear_f16", True, srcs, weight, bias, resid)
+        (Bn, N), C_out = mats[0][0].shape[:2], W.shape[0]
         nv = self._dnet_counts(n_verts, Bn)
         out_dtype = out_dtype if out is None else out.dtype
         if out_dtype not in _HALF_OR_SINGLE:
             raise ValueError("dnet_linear_f16: the output is float32 or float16")
         out, ldo = self._dnet_out(out, Bn, N, C_out, "dnet_linear_f16", out_dtype)
-        a = [(m, m.shape[2], ld, _flag(m)) for m, ld in mats] + [(None, 0, 0, _lib.DM_F32)] * (3 - len(mats))
-        self._chk(self.lib.dm_dnet_linear_f16(self.ctx, Bn, N, C_out, len(mats), _ptr(a[0][0]), *a[0][1:], _ptr(a[1][0]), *a[1][1:], _ptr(a[2][0]), *a[2][1:],
-                                              _ptr(W), ldw, _ptr(bias), _lib.DM_F32 if bias is None else _flag(bias), _ptr(R), ldr, 1 if relu else 0,
-                                              _ptr(nv), _flag(out), _ptr(out), ldo))
+        a = self._dnet_src_args(mats, True)
+        self._chk(self.lib.dm_dnet_linear_f16(self.ctx, Bn, N, C_out, len(mats), *a[0], *a[1], *a[2], _ptr(W), ldw, _ptr(bias),
+                                              _lib.DM_F32 if bias is None else _flag(bias), _ptr(R), ldr, 1 if relu else 0, _ptr(nv), _flag(out),
+                                              _ptr(out), ldo))
         return out[0] if flat else out
 
     def dnet_diffuse_f16(self, x, evecs_h, mevecs_h, e1, e2, evals, times, n_verts=None, out=None):
@@ -572,27 +477,7 @@ class _DiffusionNetOps:
     def dnet_gradient_features_f16(self, x, row_len, cols, gx, gy, A_re, A_im=None, n_verts=None, out=None):
         """dnet_gradient_features with float16 A_re / A_im (dm_dnet_gradfeat_f16): the gradients come from the float32 rows and the
         float32 x in float32 and are rounded only as operands of the products with the matrices.  Returns float32."""
-        X, ldx = self._strided(x, torch.float32, "x")
-        Bn, N, Cw = X.shape
-        row_len = self._dev(row_len, torch.int32, "row_len")
-        cols = self._dev(cols, torch.int32, "cols")
-        gx = self._dev(gx, torch.float32, "gx")
-        gy = self._dev(gy, torch.float32, "gy")
-        if cols.dim() != 3 or tuple(cols.shape[:2]) != (Bn, N) or gx.shape != cols.shape or gy.shape != cols.shape or tuple(row_len.shape) != (Bn, N):
-            raise ValueError("dnet_gradient_features_f16: row_len (B,N), cols / gx / gy (B,N,nnz)")
-        Are, lda = self._strided(A_re, torch.float16, "A_re")
-        Aim = None
-        if A_im is not None:
-            Aim, lda2 = self._strided(A_im, torch.float16, "A_im")
-            if lda2 != lda:
-                Are, Aim, lda = Are.contiguous(), Aim.contiguous(), Cw
-        if tuple(Are.shape) != (Cw, Cw) or (Aim is not None and tuple(Aim.shape) != (Cw, Cw)):
-            raise ValueError("dnet_gradient_features_f16: A_re / A_im must be (C, C)")
-        nv = self._dnet_counts(n_verts, Bn)
-        out, ldo = self._dnet_out(out, Bn, N, Cw, "dnet_gradient_features_f16")
-        self._chk(self.lib.dm_dnet_gradfeat_f16(self.ctx, Bn, N, Cw, cols.shape[2], _ptr(row_len), _ptr(cols), _ptr(gx), _ptr(gy), _ptr(X), ldx,
-                                                _ptr(Are), _ptr(Aim), lda, _ptr(nv), _ptr(out), ldo))
-        return out
+        return self._dnet_gradient_features("dnet_gradient_features_f16", True, x, row_len, cols, gx, gy, A_re, A_im, n_verts, out)
 
     def diffusion_net_forward(self, weights, packed, x, out_dtype=None):
         """A whole DiffusionNet (inference) on a padded batch: first_lin, per block diffuse -> gradient features -> the MLP (its first

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dm_corners.h"
+#include "dm_dnet_common.h"
 
 struct dnet_rows_out {
     int32_t* rowlen; int32_t* rowcol;                 // (B, N), (B, N, LAP_MAXROW)
@@ -231,17 +232,6 @@ struct dnet_rows_layout {
 };
 }  // namespace
 
-// n_verts lives on the device and sizes every per-mesh loop: read it back once and refuse counts outside [1, N]
-static int dnet_check_counts(dm_ctx* ctx, int B, int N, const int32_t* n_verts) {
-    if (!n_verts) return DM_OK;
-    std::vector<int32_t> h((size_t)B);
-    DM_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), n_verts, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; ++b)
-        if (h[b] < 1 || h[b] > N) return dm_fail(ctx, DM_EINVAL, "diffusion operators: n_verts[%d] = %d outside [1, %d]", b, (int)h[b], N);
-    return DM_OK;
-}
-
 extern "C" size_t dm_dnet_rows_bytes(int B, int N, int nt) {
     if (B <= 0 || N <= 0 || nt <= 0) return 0;
     return dm_align_up((size_t)B * N * 4) * 3 + dm_align_up((size_t)B * (N + 1) * 4) + dm_align_up((size_t)B * 3 * nt * 4) +
@@ -260,7 +250,7 @@ extern "C" int dm_dnet_rows(dm_ctx* ctx, int B, int N, int nt, const int32_t* tr
     DM_REQUIRE(ctx, tri && verts && rows && frames && info && max_row, "null pointer");
     DM_REQUIRE(ctx, denom_eps >= 0.0 && grad_eps > 0.0, "denom_eps >= 0, grad_eps > 0");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dnet_check_counts(ctx, B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "diffusion operators", B, N, n_verts)) return rc;
     dnet_rows_layout r(rows, B, N, nt);
     int32_t* bad = r.maxlen + B;
     lap_args a{B, N, nt, tri, nullptr, verts, 1.0, n_verts};
@@ -296,7 +286,7 @@ extern "C" int dm_dnet_ell(dm_ctx* ctx, int B, int N, int nt, const void* rows, 
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const dnet_rows_layout r(const_cast<void*>(rows), B, N, nt);
     // what stage 1 left in `rows` decides whether nnz is wide enough (a narrower width would drop entries): read the row maxima back
-    if (int rc = dnet_check_counts(ctx, B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "diffusion operators", B, N, n_verts)) return rc;
     std::vector<int32_t> h((size_t)B + 1);
     DM_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), r.maxlen, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
     DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -15,11 +15,13 @@
 // of its staging loads.  A functor either tests its indices and loads behind the test, or -- the weight gradient, whose contraction
 // is the longest and whose grid the smallest -- loads unconditionally from indices clamped into the operand and selects zero
 // afterwards, so that all loads of a stage are in flight together; measured per kernel, the faster form is kept (DESIGN.md section 4,
-// 'DiffusionNet backward').  Neither forms an address outside a mesh's rows.  A gradient with respect to a parameter contracts over the vertices: one chain per mesh into the caller's
-// workspace, then one pass that adds the meshes in ascending order.
-#include <math.h>
-
-#include "dm_internal.h"
+// 'DiffusionNet backward').  Neither forms an address outside a mesh's rows.  A gradient with respect to a parameter contracts over
+// the vertices: one chain per mesh into the caller's workspace, then one pass that adds the meshes in ascending order.
+//
+// This file holds what is the fp32 family's own: the tile kernel, the operands of the diffusion and dm_dnet_diffuse_bwd_f32.  The
+// operand functors of the linear layer and of the gradient features, the elementwise kernels, the argument checks and the bodies of the
+// other three entries are those of dm_dnet_bwd_common.h for T = float, shared with dm_dnet_half_bwd.hip.
+#include "dm_dnet_bwd_common.h"
 
 typedef float db_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -28,6 +30,7 @@ constexpr int DB_T = 64;          // outputs per workgroup side
 constexpr int DB_KC = 32;         // contraction depth per stage
 constexpr int DB_LD = DB_T + 1;   // LDS row stride of a stage [kk][row]
 constexpr int DB_KMAX = 1024;     // dm_dnet_diffuse_f32's limit: a forward pass beyond it does not exist
+static_assert(DB_T == DNB_T, "the shared functors skip whole tiles of this side");
 
 __device__ __forceinline__ int db_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
 
@@ -94,91 +97,13 @@ int db_launch(dm_ctx* ctx, const char* name, int B, const Op& op) {
     return DM_OK;
 }
 
-// out[r, c] = ((part_0 + part_1) + ..)[r, c] over the B meshes in ascending order
-__global__ void db_sum_meshes_kernel(const float* part, int B, int R, int Cc, int ldp, long long mesh_stride, float* out, int ldo) {
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)R * Cc) return;
-    const int rr = (int)(e / Cc), c = (int)(e - (long long)rr * Cc);
-    const float* p = part + (long long)rr * ldp + c;
-    float s = p[0];
-    for (int b = 1; b < B; ++b) s += p[b * mesh_stride];
-    out[(long long)rr * ldo + c] = s;
-}
-
-int db_sum_meshes(dm_ctx* ctx, const float* part, int B, int R, int Cc, int ldp, long long mesh_stride, float* out, int ldo) {
-    DM_LAUNCH(ctx, "dnet_bwd_sum", db_sum_meshes_kernel, dim3((unsigned)(((long long)R * Cc + 255) / 256)), dim3(256), 0, part, B, R, Cc, ldp,
-              mesh_stride, out, ldo);
-    return DM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- linear
-struct lin_common {
-    int N, Cout, Ktot;
-    const int32_t* nv;
-    const float* dY; int lddy; const float* Y; int ldy;       // Y null: no activation
-    // dZ[b,i,o] = dY ⊙ [Y > 0]: applied while a tile is staged, never stored
-    __device__ __forceinline__ float dz(int b, int nvb, int i, int o) const {
-        if (i >= nvb || o >= Cout) return 0.f;
-        const long long br = (long long)b * N + i;
-        const float v = dY[br * lddy + o];
-        return (Y && !(Y[br * ldy + o] > 0.f)) ? 0.f : v;
-    }
-    __device__ __forceinline__ float dz_clamped(int b, int nvb, int i, int o) const {
-        const long long br = (long long)b * N + min(i, nvb - 1);
-        const int oc = min(o, Cout - 1);
-        const float v = dY[br * lddy + oc];
-        const float y = Y ? Y[br * ldy + oc] : 1.f;
-        return (i < nvb && o < Cout && y > 0.f) ? v : 0.f;
-    }
-};
-
-struct lin_data_op : lin_common {
-    const float* W; int ldw;
-    float* out[3]; int w[3]; int ld[3];
-    __device__ __host__ __forceinline__ int rows() const { return N; }
-    __device__ __host__ __forceinline__ int cols() const { return Ktot; }
-    __device__ __forceinline__ int depth(int) const { return Cout; }
-    __device__ __forceinline__ int source(int& k) const {
-        int s = 0;
-        if (k >= w[0]) { k -= w[0]; s = 1; if (k >= w[1]) { k -= w[1]; s = 2; } }
-        return s;
-    }
-    __device__ __forceinline__ bool skip(int col0) const {       // every column of the tile belongs to a source without an output
-        int lo = col0, hi = min(col0 + DB_T, Ktot) - 1;
-        const int s0 = source(lo), s1 = source(hi);
-        for (int s = s0; s <= s1; ++s)
-            if (out[s]) return false;
-        return true;
-    }
-    __device__ __forceinline__ float a(int, int b, int nvb, int i, int o) const { return dz(b, nvb, i, o); }
-    __device__ __forceinline__ float b(int, int, int, int o, int k) const { return (o < Cout && k < Ktot) ? W[(long long)o * ldw + k] : 0.f; }
-    __device__ __forceinline__ void store(int b, int nvb, int i, int k, float p1, float, float, float) const {
-        const int s = source(k);
-        float* o = s == 0 ? out[0] : (s == 1 ? out[1] : out[2]);
-        const long long l = s == 0 ? ld[0] : (s == 1 ? ld[1] : ld[2]);
-        if (o) o[((long long)b * N + i) * l + k] = i < nvb ? p1 : 0.f;
-    }
-};
-
-struct lin_weight_op : lin_common {
-    const float* src[3]; int w[3]; int ld[3];
-    float* part;                                               // [B][Cout][Ktot + 1]: column Ktot is the bias
-    __device__ __host__ __forceinline__ int rows() const { return Cout; }
-    __device__ __host__ __forceinline__ int cols() const { return Ktot + 1; }
-    __device__ __forceinline__ int depth(int nvb) const { return nvb; }
-    __device__ __forceinline__ bool skip(int) const { return false; }
-    __device__ __forceinline__ float a(int, int b, int nvb, int o, int i) const { return dz_clamped(b, nvb, i, o); }
-    __device__ __forceinline__ float b(int, int b, int nvb, int i, int k) const {
-        const int kc = min(k, Ktot - 1);
-        const int s = kc < w[0] ? 0 : (kc < w[0] + w[1] ? 1 : 2);
-        const float* sp = s == 0 ? src[0] : (s == 1 ? src[1] : src[2]);
-        const long long l = s == 0 ? ld[0] : (s == 1 ? ld[1] : ld[2]);
-        const float v = sp[((long long)b * N + min(i, nvb - 1)) * l + (kc - (s == 0 ? 0 : (s == 1 ? w[0] : w[0] + w[1])))];
-        return i < nvb ? (k < Ktot ? v : (k == Ktot ? 1.f : 0.f)) : 0.f;      // column Ktot: db[o] = sum_i dZ[i, o], fma(dz, 1, s) = s + dz
-    }
-    __device__ __forceinline__ void store(int b, int, int o, int k, float p1, float, float, float) const {
-        part[((long long)b * Cout + o) * (Ktot + 1) + k] = p1;
-    }
+struct db_family {
+    static constexpr const char *sum = "dnet_bwd_sum", *lin_data = "dnet_linear_bwd_data", *lin_weight = "dnet_linear_bwd_weight",
+                                *gf_gather = "dnet_gradfeat_bwd_gather", *gf_fwd = "dnet_gradfeat_bwd_fwd", *gf_grad = "dnet_gradfeat_bwd_grad",
+                                *gf_gather_t = "dnet_gradfeat_bwd_gather_t", *gf_param = "dnet_gradfeat_bwd_param";
+    // (one schedule for every contraction: the weight gradient's loads are clamped instead, dnb_lin_common::dz_clamped)
+    template <int NA, int NB, bool A_TILE, bool B_TILE, bool OVER_VERTS, class Op>
+    static int tile(dm_ctx* ctx, const char* name, int B, const Op& op) { return db_launch<NA, NB, A_TILE, B_TILE>(ctx, name, B, op); }
 };
 
 // ---------------------------------------------------------------------------------------------------------------- diffuse
@@ -227,192 +152,15 @@ struct dif_back_op {                                           // dx = mass ⊙ 
         dx[br * lddx + c] = i < nvb ? __fmul_rn(mass[br], p1) : 0.f;
     }
 };
-
-// m_b[c] = the running sum of T[b, k, c] over ascending k from +0, left in T[b, 0, c] (read and written by this thread only)
-__global__ void dif_times_mesh_kernel(float* T, int K, int C) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (c >= C) return;
-    float* p = T + (long long)b * K * C + c;
-    float m = 0.f;
-    for (int k = 0; k < K; ++k) m += p[(long long)k * C];
-    p[0] = m;
-}
-
-// dtimes[c] = -((m_0 + m_1) + ..)
-__global__ void dif_times_kernel(const float* T, int B, int K, int C, float* dtimes) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    float tot = T[c];
-    for (int b = 1; b < B; ++b) tot += T[(long long)b * K * C + c];
-    dtimes[c] = -tot;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- gradient features
-struct gf_ws {                                                 // [B][N][C] each, rows behind a mesh's count neither written nor read
-    float* gX; float* gY; float* U; float* V; float* dgX; float* dgY;
-};
-
-// gX = G_x x, gY = G_y x: the forward's chain (gf_gather of dm_dnet_layers.hip), entries in stored order, one fmaf each
-__global__ void gf_gather_kernel(int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx, const float* gy, const float* x,
-                                 int ldx, const int32_t* nv, float* gX, float* gY) {
-    const int b = blockIdx.y;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int nvb = nv ? nv[b] : N;
-    if (e >= (long long)nvb * C) return;
-    const int row = (int)(e / C), ch = (int)(e - (long long)row * C);
-    const long long br = (long long)b * N + row;
-    const int len = min(max(row_len[br], 0), nnz);
-    const int32_t* cl = cols + br * nnz;
-    const float* vx = gx + br * nnz;
-    const float* vy = gy + br * nnz;
-    const float* xb = x + (long long)b * N * ldx + ch;
-    float sx = 0.f, sy = 0.f;
-    for (int q = 0; q < len; ++q) {
-        const int c = cl[q];
-        if ((unsigned)c >= (unsigned)nvb) continue;
-        const float xv = xb[(long long)c * ldx];
-        sx = fmaf(vx[q], xv, sx);
-        sy = fmaf(vy[q], xv, sy);
-    }
-    gX[br * C + ch] = sx;
-    gY[br * C + ch] = sy;
-}
-
-// dx = G_x^T dgX + G_y^T dgY as a gather over the rows of the transposed operators: entry q of row j adds gx_t dgX[col], then
-// gy_t dgY[col], one fmaf each, q ascending
-__global__ void gf_gather_t_kernel(int N, int C, int nnz, const int32_t* row_len, const int32_t* cols, const float* gx, const float* gy,
-                                   const float* dgX, const float* dgY, const int32_t* nv, float* dx, int lddx) {
-    const int b = blockIdx.y;
-    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (long long)N * C) return;
-    const int nvb = nv ? nv[b] : N;
-    const int row = (int)(e / C), ch = (int)(e - (long long)row * C);
-    const long long br = (long long)b * N + row;
-    float s = 0.f;
-    if (row < nvb) {
-        const int len = min(max(row_len[br], 0), nnz);
-        const int32_t* cl = cols + br * nnz;
-        const float* vx = gx + br * nnz;
-        const float* vy = gy + br * nnz;
-        for (int q = 0; q < len; ++q) {
-            const int c = cl[q];
-            if ((unsigned)c >= (unsigned)nvb) continue;
-            const long long o = ((long long)b * N + c) * C + ch;
-            s = fmaf(vx[q], dgX[o], s);
-            s = fmaf(vy[q], dgY[o], s);
-        }
-    }
-    dx[br * lddx + ch] = s;
-}
-
-struct gf_common {
-    int N, C;
-    const int32_t* nv;
-    gf_ws ws;
-    const float* Are; const float* Aim; int lda;              // Aim null: no rotation
-    __device__ __host__ __forceinline__ int cols() const { return C; }
-    __device__ __forceinline__ bool skip(int) const { return false; }
-    __device__ __forceinline__ float act(const float* p, int b, int nvb, int i, int c) const {
-        return (i < nvb && c < C) ? p[((long long)b * N + i) * C + c] : 0.f;
-    }
-    __device__ __forceinline__ float mat(int w, int row, int col) const {      // A_re (w = 0) or A_im [row][col]
-        return (row < C && col < C) ? (w ? Aim : Are)[(long long)row * lda + col] : 0.f;
-    }
-};
-
-struct gf_fwd_op : gf_common {                                 // B_re, B_im, out; p = dO (1 - out^2); U, V; the first terms of dgX, dgY
-    const float* dO; int lddo;
-    __device__ __host__ __forceinline__ int rows() const { return N; }
-    __device__ __forceinline__ int depth(int) const { return C; }
-    __device__ __forceinline__ float a(int w, int b, int nvb, int i, int k) const { return act(w ? ws.gY : ws.gX, b, nvb, i, k); }
-    __device__ __forceinline__ float b(int w, int, int, int k, int c) const { return mat(w, c, k); }
-    __device__ __forceinline__ void store(int b, int nvb, int i, int c, float p1, float p2, float p3, float p4) const {
-        if (i >= nvb) return;
-        const long long br = (long long)b * N + i, o = br * C + c;
-        const float sx = ws.gX[o], sy = ws.gY[o];
-        const float bre = Aim ? p1 - p2 : p1, bim = Aim ? p3 + p4 : p3;
-        const float out = tanhf(fmaf(sx, bre, __fmul_rn(sy, bim)));
-        const float p = __fmul_rn(dO[br * lddo + c], fmaf(-out, out, 1.f));
-        ws.U[o] = __fmul_rn(p, sx);
-        ws.V[o] = __fmul_rn(p, sy);
-        ws.dgX[o] = __fmul_rn(p, bre);
-        ws.dgY[o] = __fmul_rn(p, bim);
-    }
-};
-
-struct gf_grad_op : gf_common {                                // dgX += U A_re + V A_im, dgY += V A_re - U A_im
-    __device__ __host__ __forceinline__ int rows() const { return N; }
-    __device__ __forceinline__ int depth(int) const { return C; }
-    __device__ __forceinline__ float a(int w, int b, int nvb, int i, int c) const { return act(w ? ws.V : ws.U, b, nvb, i, c); }
-    __device__ __forceinline__ float b(int w, int, int, int c, int k) const { return mat(w, c, k); }
-    __device__ __forceinline__ void store(int b, int nvb, int i, int k, float p1, float p2, float p3, float p4) const {
-        if (i >= nvb) return;
-        const long long o = ((long long)b * N + i) * C + k;
-        const float x0 = ws.dgX[o] + p1, y0 = Aim ? ws.dgY[o] - p4 : ws.dgY[o];
-        ws.dgX[o] = Aim ? x0 + p2 : x0;
-        ws.dgY[o] = y0 + p3;
-    }
-};
-
-struct gf_param_op : gf_common {                               // per mesh: dA_re = U^T gX + V^T gY, dA_im = V^T gX - U^T gY
-    float* Pre; float* Pim;                                    // [B][C][C]
-    __device__ __host__ __forceinline__ int rows() const { return C; }
-    __device__ __forceinline__ int depth(int nvb) const { return nvb; }
-    __device__ __forceinline__ float a(int w, int b, int nvb, int c, int i) const { return act(w ? ws.V : ws.U, b, nvb, i, c); }
-    __device__ __forceinline__ float b(int w, int b, int nvb, int i, int k) const { return act(w ? ws.gY : ws.gX, b, nvb, i, k); }
-    __device__ __forceinline__ void store(int b, int, int c, int k, float p1, float p2, float p3, float p4) const {
-        const long long o = ((long long)b * C + c) * C + k;
-        Pre[o] = p1 + p2;
-        if (Aim) Pim[o] = p3 - p4;
-    }
-};
-
-// n_verts lives on the device and bounds every load: read it back once and refuse counts outside [1, N]
-int db_check_counts(dm_ctx* ctx, const char* who, int B, int N, const int32_t* n_verts) {
-    if (!n_verts) return DM_OK;
-    std::vector<int32_t> h((size_t)B);
-    DM_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), n_verts, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; ++b)
-        if (h[b] < 1 || h[b] > N) return dm_fail(ctx, DM_EINVAL, "%s: n_verts[%d] = %d outside [1, %d]", who, b, (int)h[b], N);
-    return DM_OK;
-}
-
-// the checks that the two linear entries share; fills w / ld of the absent sources with zeros
-int db_lin_check(dm_ctx* ctx, int B, int N, int C_out, int n_src, const void* const* ptr, bool need_all, int* w, int* ld, const float* dY, int lddy,
-                 const float* Y, int ldy, int act, long long* ktot) {
-    DM_REQUIRE(ctx, B > 0 && N > 0 && C_out > 0 && B <= 65535, "sizes must be positive, B <= 65535");
-    DM_REQUIRE(ctx, n_src >= 1 && n_src <= 3, "one to three sources");
-    DM_REQUIRE(ctx, act == 0 || act == 1, "act: 0 none, 1 ReLU");
-    *ktot = 0;
-    for (int s = 0; s < 3; ++s) {
-        if (s >= n_src) { w[s] = 0; ld[s] = 0; continue; }
-        DM_REQUIRE(ctx, !need_all || ptr[s] != nullptr, "null source");
-        DM_REQUIRE(ctx, w[s] > 0 && ld[s] >= w[s], "a source needs width > 0 and ld >= width");
-        *ktot += w[s];
-    }
-    DM_REQUIRE(ctx, *ktot <= (1 << 24), "summed source width");
-    DM_REQUIRE(ctx, dY && lddy >= C_out, "dY, lddy >= C_out");
-    DM_REQUIRE(ctx, !act || (Y && ldy >= C_out), "act = 1 needs the saved output Y, ldy >= C_out");
-    return DM_OK;
-}
 }  // namespace
 
 extern "C" int dm_dnet_linear_bwd_data_f32(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* dY, int lddy, const float* Y /*nullable*/,
                                            int ldy, int act, const float* W, int ldw, const int32_t* n_verts /*nullable*/, float* d0 /*nullable*/,
                                            int w0, int ld0, float* d1 /*nullable*/, int w1, int ld1, float* d2 /*nullable*/, int w2, int ld2) {
     if (!ctx) return DM_EINVAL;
-    const void* ptr[3] = {d0, d1, d2};
+    float* d[3] = {d0, d1, d2};
     int w[3] = {w0, w1, w2}, ld[3] = {ld0, ld1, ld2};
-    long long ktot = 0;
-    if (int rc = db_lin_check(ctx, B, N, C_out, n_src, ptr, false, w, ld, dY, lddy, Y, ldy, act, &ktot)) return rc;
-    DM_REQUIRE(ctx, W && ldw >= (int)ktot, "W, ldw >= summed widths");
-    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = db_check_counts(ctx, "dm_dnet_linear_bwd_data_f32", B, N, n_verts)) return rc;
-    float* out[3] = {d0, n_src > 1 ? d1 : nullptr, n_src > 2 ? d2 : nullptr};
-    if (!out[0] && !out[1] && !out[2]) return DM_OK;
-    lin_data_op op{{N, C_out, (int)ktot, n_verts, dY, lddy, act ? Y : nullptr, ldy}, W, ldw, {out[0], out[1], out[2]}, {w[0], w[1], w[2]}, {ld[0], ld[1], ld[2]}};
-    return db_launch<1, 1, false, true>(ctx, "dnet_linear_bwd_data", B, op);
+    return dnb_linear_bwd_data<float, db_family>(ctx, __func__, B, N, C_out, n_src, dY, lddy, Y, ldy, act, W, ldw, n_verts, d, w, ld);
 }
 
 extern "C" size_t dm_dnet_linear_bwd_bytes(int B, int C_out, int k_tot) {
@@ -425,25 +173,10 @@ extern "C" int dm_dnet_linear_bwd_weight_f32(dm_ctx* ctx, int B, int N, int C_ou
                                              const float* src2, int w2, int ld2, const int32_t* n_verts /*nullable*/, void* ws,
                                              float* dW /*nullable*/, int lddw, float* db /*nullable*/) {
     if (!ctx) return DM_EINVAL;
-    const void* ptr[3] = {src0, src1, src2};
+    const void* src[3] = {src0, src1, src2};
     int w[3] = {w0, w1, w2}, ld[3] = {ld0, ld1, ld2};
-    long long ktot = 0;
-    if (int rc = db_lin_check(ctx, B, N, C_out, n_src, ptr, true, w, ld, dY, lddy, Y, ldy, act, &ktot)) return rc;
-    DM_REQUIRE(ctx, ws != nullptr, "null workspace");
-    DM_REQUIRE(ctx, !dW || lddw >= (int)ktot, "lddw >= summed widths");
-    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = db_check_counts(ctx, "dm_dnet_linear_bwd_weight_f32", B, N, n_verts)) return rc;
-    if (!dW && !db) return DM_OK;
-    const int K = (int)ktot;
-    lin_weight_op op{{N, C_out, K, n_verts, dY, lddy, act ? Y : nullptr, ldy}, {src0, n_src > 1 ? src1 : nullptr, n_src > 2 ? src2 : nullptr},
-                     {w[0], w[1], w[2]}, {ld[0], ld[1], ld[2]}, (float*)ws};
-    if (int rc = db_launch<1, 1, true, true>(ctx, "dnet_linear_bwd_weight", B, op)) return rc;
-    const long long stride = (long long)C_out * (K + 1);
-    if (dW)
-        if (int rc = db_sum_meshes(ctx, (const float*)ws, B, C_out, K, K + 1, stride, dW, lddw)) return rc;
-    if (db)
-        if (int rc = db_sum_meshes(ctx, (const float*)ws + K, B, C_out, 1, K + 1, stride, db, 1)) return rc;
-    return DM_OK;
+    return dnb_linear_bwd_weight<float, db_family>(ctx, __func__, B, N, C_out, n_src, dY, lddy, Y, ldy, act, src, w, ld, nullptr, n_verts, ws, dW, lddw,
+                                                   db);
 }
 
 extern "C" size_t dm_dnet_diffuse_bwd_bytes(int B, int K, int C) {
@@ -462,7 +195,7 @@ extern "C" int dm_dnet_diffuse_bwd_f32(dm_ctx* ctx, int B, int N, int K, int C, 
     DM_REQUIRE(ctx, !dtimes || (x && ldx >= C), "dtimes needs the saved x, ldx >= C");
     DM_REQUIRE(ctx, !dx || lddx >= C, "lddx >= C");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = db_check_counts(ctx, "dm_dnet_diffuse_bwd_f32", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_diffuse_bwd_f32", B, N, n_verts)) return rc;
     if (!dx && !dtimes) return DM_OK;
     float* H = (float*)ws;
     float* T = dtimes ? H + (size_t)B * K * C : nullptr;
@@ -474,8 +207,8 @@ extern "C" int dm_dnet_diffuse_bwd_f32(dm_ctx* ctx, int B, int N, int K, int C, 
         if (int rc = db_launch<1, 1, false, true>(ctx, "dnet_diffuse_bwd_back", B, bk)) return rc;
     }
     if (dtimes) {
-        DM_LAUNCH(ctx, "dnet_diffuse_bwd_times", dif_times_mesh_kernel, dim3(dm_cdiv(C, 64), B), dim3(64), 0, T, K, C);
-        DM_LAUNCH(ctx, "dnet_diffuse_bwd_times", dif_times_kernel, dim3(dm_cdiv(C, 64)), dim3(64), 0, (const float*)T, B, K, C, dtimes);
+        DM_LAUNCH(ctx, "dnet_diffuse_bwd_times", dnb_times_mesh_kernel, dim3(dm_cdiv(C, 64), B), dim3(64), 0, T, K, C);
+        DM_LAUNCH(ctx, "dnet_diffuse_bwd_times", dnb_times_kernel, dim3(dm_cdiv(C, 64)), dim3(64), 0, (const float*)T, B, K, C, dtimes);
     }
     return DM_OK;
 }
@@ -491,41 +224,6 @@ extern "C" int dm_dnet_gradfeat_bwd_f32(dm_ctx* ctx, int B, int N, int C, int nn
                                         const float* A_im /*nullable*/, int lda, const int32_t* n_verts /*nullable*/, void* ws, float* dx /*nullable*/,
                                         int lddx, float* dA_re /*nullable*/, float* dA_im /*nullable*/, int ldda) {
     if (!ctx) return DM_EINVAL;
-    DM_REQUIRE(ctx, B > 0 && N > 0 && C > 0 && nnz > 0 && B <= 65535, "sizes must be positive, B <= 65535");
-    DM_REQUIRE(ctx, row_len && cols && gx && gy && dO && x && A_re && ws, "null pointer");
-    DM_REQUIRE(ctx, ldx >= C && lddo >= C && lda >= C, "ldx >= C, lddo >= C, lda >= C");
-    DM_REQUIRE(ctx, !dx || (nnz_t > 0 && row_len_t && cols_t && gx_t && gy_t && lddx >= C), "dx needs the transposed rows, lddx >= C");
-    DM_REQUIRE(ctx, (!dA_re && !dA_im) || ldda >= C, "ldda >= C");
-    DM_REQUIRE(ctx, !dA_im || A_im, "dA_im without A_im");
-    DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = db_check_counts(ctx, "dm_dnet_gradfeat_bwd_f32", B, N, n_verts)) return rc;
-    if (!dx && !dA_re && !dA_im) return DM_OK;
-    const size_t plane = (size_t)B * N * C;
-    float* w = (float*)ws;
-    gf_ws g{w, w + plane, w + 2 * plane, w + 3 * plane, w + 4 * plane, w + 5 * plane};
-    float* Pre = w + 6 * plane;
-    float* Pim = Pre + (size_t)B * C * C;
-    const unsigned nblk = (unsigned)(((long long)N * C + 255) / 256);
-    DM_LAUNCH(ctx, "dnet_gradfeat_bwd_gather", gf_gather_kernel, dim3(nblk, B), dim3(256), 0, N, C, nnz, row_len, cols, gx, gy, x, ldx, n_verts, g.gX, g.gY);
-    gf_common cm{N, C, n_verts, g, A_re, A_im, lda};
-    gf_fwd_op f{cm, dO, lddo};
-    if (int rc = A_im ? db_launch<2, 2, false, false>(ctx, "dnet_gradfeat_bwd_fwd", B, f) : db_launch<2, 1, false, false>(ctx, "dnet_gradfeat_bwd_fwd", B, f))
-        return rc;
-    if (dx) {
-        gf_grad_op gr{cm};
-        if (int rc = A_im ? db_launch<2, 2, false, true>(ctx, "dnet_gradfeat_bwd_grad", B, gr) : db_launch<2, 1, false, true>(ctx, "dnet_gradfeat_bwd_grad", B, gr))
-            return rc;
-        DM_LAUNCH(ctx, "dnet_gradfeat_bwd_gather_t", gf_gather_t_kernel, dim3(nblk, B), dim3(256), 0, N, C, nnz_t, row_len_t, cols_t, gx_t, gy_t,
-                  (const float*)g.dgX, (const float*)g.dgY, n_verts, dx, lddx);
-    }
-    if (dA_re || dA_im) {
-        gf_param_op pr{cm, Pre, Pim};
-        if (int rc = db_launch<2, 2, true, true>(ctx, "dnet_gradfeat_bwd_param", B, pr)) return rc;
-        const long long stride = (long long)C * C;
-        if (dA_re)
-            if (int rc = db_sum_meshes(ctx, Pre, B, C, C, C, stride, dA_re, ldda)) return rc;
-        if (dA_im)
-            if (int rc = db_sum_meshes(ctx, Pim, B, C, C, C, stride, dA_im, ldda)) return rc;
-    }
-    return DM_OK;
+    return dnb_gradfeat_bwd<float, db_family>(ctx, __func__, B, N, C, nnz, row_len, cols, gx, gy, nnz_t, row_len_t, cols_t, gx_t, gy_t, dO, lddo, x, ldx,
+                                              A_re, A_im, lda, n_verts, ws, dx, lddx, dA_re, dA_im, ldda);
 }

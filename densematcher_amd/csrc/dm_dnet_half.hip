@@ -21,7 +21,7 @@
 
 #include <hip/hip_fp16.h>
 
-#include "dm_internal.h"
+#include "dm_dnet_common.h"
 
 typedef float dh_f32x16 __attribute__((ext_vector_type(16)));
 typedef float dh_f32x4 __attribute__((ext_vector_type(4)));
@@ -566,20 +566,6 @@ __global__ void __launch_bounds__(256) dnet_gradfeat_f16_rows_kernel(hg_args a, 
         }
     }
 }
-
-// n_verts lives on the device and bounds every load: read it back once and refuse counts outside [1, N]
-int dh_check_counts(dm_ctx* ctx, const char* who, int B, int N, const int32_t* n_verts) {
-    if (!n_verts) return DM_OK;
-    std::vector<int32_t> h((size_t)B);
-    DM_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), n_verts, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; ++b)
-        if (h[b] < 1 || h[b] > N) return dm_fail(ctx, DM_EINVAL, "%s: n_verts[%d] = %d outside [1, %d]", who, b, (int)h[b], N);
-    return DM_OK;
-}
-
-bool dh_dtype(int d) { return d == DM_F16 || d == DM_F32; }
-bool dh_al(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
 }  // namespace
 
 extern "C" int dm_dnet_linear_f16(dm_ctx* ctx, int B, int N, int C_out, int n_src, const void* src0, int w0, int ld0, int dtype0, const void* src1,
@@ -591,25 +577,25 @@ extern "C" int dm_dnet_linear_f16(dm_ctx* ctx, int B, int N, int C_out, int n_sr
     DM_REQUIRE(ctx, dm_cdiv(N, 64) <= 65535, "N <= 65535 * 64");
     DM_REQUIRE(ctx, n_src >= 1 && n_src <= 3, "one to three sources");
     DM_REQUIRE(ctx, act == 0 || act == 1, "act: 0 none, 1 ReLU");
-    DM_REQUIRE(ctx, dh_dtype(out_dtype) && (!bias || dh_dtype(bias_dtype)), "bias and output dtype: DM_F16 or DM_F32");
+    DM_REQUIRE(ctx, dm_dnet_dtype(out_dtype) && (!bias || dm_dnet_dtype(bias_dtype)), "bias and output dtype: DM_F16 or DM_F32");
     const void* src[3] = {src0, src1, src2};
     int w[3] = {w0, w1, w2}, ld[3] = {ld0, ld1, ld2}, dt[3] = {dtype0, dtype1, dtype2};
     long long ktot = 0;
     for (int s = 0; s < 3; ++s) {
         if (s >= n_src) { src[s] = nullptr; w[s] = 0; ld[s] = 0; dt[s] = DM_F32; continue; }
         DM_REQUIRE(ctx, src[s] != nullptr, "null source");
-        DM_REQUIRE(ctx, dh_dtype(dt[s]), "source dtype: DM_F16 or DM_F32");
+        DM_REQUIRE(ctx, dm_dnet_dtype(dt[s]), "source dtype: DM_F16 or DM_F32");
         DM_REQUIRE(ctx, w[s] > 0 && ld[s] >= w[s], "a source needs width > 0 and ld >= width");
-        DM_REQUIRE(ctx, dh_al(src[s], dt[s] == DM_F16 ? 2 : 4), "a source must be aligned to its element");
+        DM_REQUIRE(ctx, dm_dnet_al(src[s], dt[s] == DM_F16 ? 2 : 4), "a source must be aligned to its element");
         ktot += w[s];
     }
     DM_REQUIRE(ctx, ktot <= (1 << 24), "summed source width");
     DM_REQUIRE(ctx, W && out, "null pointer");
-    DM_REQUIRE(ctx, dh_al(W, 2) && dh_al(out, out_dtype == DM_F16 ? 2 : 4), "W and out must be aligned to their elements");
+    DM_REQUIRE(ctx, dm_dnet_al(W, 2) && dm_dnet_al(out, out_dtype == DM_F16 ? 2 : 4), "W and out must be aligned to their elements");
     DM_REQUIRE(ctx, ldw >= (int)ktot && ldo >= C_out, "ldw >= summed widths, ldo >= C_out");
     DM_REQUIRE(ctx, !resid || ldr >= C_out, "ldr >= C_out");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dh_check_counts(ctx, "dm_dnet_linear_f16", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_linear_f16", B, N, n_verts)) return rc;
     hl_args a{N, C_out, (int)ktot, {src[0], src[1], src[2]}, {w[0], w[1], w[2]}, {ld[0], ld[1], ld[2]},
               {dt[0] == DM_F16, dt[1] == DM_F16, dt[2] == DM_F16}, reinterpret_cast<const _Float16*>(W), ldw, bias, bias_dtype == DM_F16,
               resid, ldr, act, n_verts, out, out_dtype == DM_F16, ldo};
@@ -627,11 +613,11 @@ extern "C" int dm_dnet_diffuse_f16(dm_ctx* ctx, int B, int N, int K, int C, cons
     DM_REQUIRE(ctx, B > 0 && N > 0 && K > 0 && C > 0 && B <= 65535, "sizes must be positive, B <= 65535");
     DM_REQUIRE(ctx, K <= DH_KMAX, "K <= 1024: the 32 x K spectrum of a workgroup has to fit in LDS");
     DM_REQUIRE(ctx, x && evecs_h && mevecs_h && e1 && e2 && evals && times && out, "null pointer");
-    DM_REQUIRE(ctx, dh_dtype(times_dtype), "times dtype: DM_F16 or DM_F32");
-    DM_REQUIRE(ctx, dh_al(evecs_h, 2) && dh_al(mevecs_h, 2) && dh_al(times, times_dtype == DM_F16 ? 2 : 4), "operands must be aligned to their elements");
+    DM_REQUIRE(ctx, dm_dnet_dtype(times_dtype), "times dtype: DM_F16 or DM_F32");
+    DM_REQUIRE(ctx, dm_dnet_al(evecs_h, 2) && dm_dnet_al(mevecs_h, 2) && dm_dnet_al(times, times_dtype == DM_F16 ? 2 : 4), "operands must be aligned to their elements");
     DM_REQUIRE(ctx, ldx >= C && ldo >= C && lde >= K && ldm >= K, "ldx >= C, ldo >= C, lde >= K, ldm >= K");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dh_check_counts(ctx, "dm_dnet_diffuse_f16", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_diffuse_f16", B, N, n_verts)) return rc;
     const int Kpad = dm_cdiv(K, 32) * 32;
     const size_t lds = ((size_t)DH_CT * (Kpad + 8) + (size_t)DH_KG * DH_VLD + (size_t)DH_CT * DH_VLD) * sizeof(_Float16);
     if (int rc = dm_grant_lds(ctx, (const void*)dnet_diffuse_f16_kernel, lds)) return rc;
@@ -648,10 +634,10 @@ extern "C" int dm_dnet_gradfeat_f16(dm_ctx* ctx, int B, int N, int C, int nnz, c
     DM_REQUIRE(ctx, B > 0 && N > 0 && C > 0 && nnz > 0 && B <= 65535, "sizes must be positive, B <= 65535");
     DM_REQUIRE(ctx, dm_cdiv(N, DH_T) <= 65535, "N <= 65535 * 64");
     DM_REQUIRE(ctx, row_len && cols && gx && gy && x && A_re && out, "null pointer");
-    DM_REQUIRE(ctx, dh_al(A_re, 2) && dh_al(A_im, 2), "A_re and A_im must be aligned to their elements");
+    DM_REQUIRE(ctx, dm_dnet_al(A_re, 2) && dm_dnet_al(A_im, 2), "A_re and A_im must be aligned to their elements");
     DM_REQUIRE(ctx, ldx >= C && ldo >= C && lda >= C, "ldx >= C, ldo >= C, lda >= C");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dh_check_counts(ctx, "dm_dnet_gradfeat_f16", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_gradfeat_f16", B, N, n_verts)) return rc;
     const int ell_lds = nnz <= DH_ELL_MAX;
     hg_args a{N, C, nnz, row_len, cols, gx, gy, x, ldx, reinterpret_cast<const _Float16*>(A_re), reinterpret_cast<const _Float16*>(A_im), lda,
               n_verts, out, ldo, ell_lds};

@@ -14,7 +14,7 @@
 // in registers while the current one is multiplied.  diffuse: one workgroup per (mesh, 32 channels); its K x 32 spectrum stays in LDS.
 #include <math.h>
 
-#include "dm_internal.h"
+#include "dm_dnet_common.h"
 
 typedef float dl_f32x16 __attribute__((ext_vector_type(16)));
 
@@ -348,17 +348,6 @@ __global__ __launch_bounds__(256) void dnet_gradfeat_kernel(gf_args a) {
         a.out[((long long)b * a.N + row) * a.ldo + col] = v;
     }
 }
-
-// n_verts lives on the device and bounds every load: read it back once and refuse counts outside [1, N]
-int dl_check_counts(dm_ctx* ctx, const char* who, int B, int N, const int32_t* n_verts) {
-    if (!n_verts) return DM_OK;
-    std::vector<int32_t> h((size_t)B);
-    DM_CHECK_HIP(ctx, hipMemcpyAsync(h.data(), n_verts, (size_t)B * 4, hipMemcpyDeviceToHost, ctx->stream));
-    DM_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int b = 0; b < B; ++b)
-        if (h[b] < 1 || h[b] > N) return dm_fail(ctx, DM_EINVAL, "%s: n_verts[%d] = %d outside [1, %d]", who, b, (int)h[b], N);
-    return DM_OK;
-}
 }  // namespace
 
 extern "C" int dm_dnet_linear_f32(dm_ctx* ctx, int B, int N, int C_out, int n_src, const float* src0, int w0, int ld0, const float* src1, int w1,
@@ -382,7 +371,7 @@ extern "C" int dm_dnet_linear_f32(dm_ctx* ctx, int B, int N, int C_out, int n_sr
     DM_REQUIRE(ctx, ldw >= (int)ktot && ldo >= C_out, "ldw >= summed widths, ldo >= C_out");
     DM_REQUIRE(ctx, !resid || ldr >= C_out, "ldr >= C_out");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dl_check_counts(ctx, "dm_dnet_linear_f32", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_linear_f32", B, N, n_verts)) return rc;
     lin_args a{N, C_out, (int)ktot, {src[0], src[1], src[2]}, {w[0], w[1], w[2]}, {ld[0], ld[1], ld[2]}, W, ldw, bias, resid, ldr, act, n_verts, out, ldo};
     DM_LAUNCH(ctx, "dnet_linear", dnet_linear_kernel, dim3(dm_cdiv(C_out, DL_T), dm_cdiv(N, DL_T), B), dim3(256), 0, a);
     return DM_OK;
@@ -396,7 +385,7 @@ extern "C" int dm_dnet_diffuse_f32(dm_ctx* ctx, int B, int N, int K, int C, cons
     DM_REQUIRE(ctx, x && mass && evals && evecs && times && out, "null pointer");
     DM_REQUIRE(ctx, ldx >= C && ldo >= C && lde >= K, "ldx >= C, ldo >= C, lde >= K");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dl_check_counts(ctx, "dm_dnet_diffuse_f32", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_diffuse_f32", B, N, n_verts)) return rc;
     const int Kpad = dm_cdiv(K, DL_KC) * DL_KC;
     const size_t lds = ((size_t)Kpad * DL_CT + DL_VT * (DL_KC + 1) + 32 * DL_CT) * sizeof(float);
     if (int rc = dm_grant_lds(ctx, (const void*)dnet_diffuse_kernel, lds)) return rc;
@@ -413,7 +402,7 @@ extern "C" int dm_dnet_gradfeat_f32(dm_ctx* ctx, int B, int N, int C, int nnz, c
     DM_REQUIRE(ctx, row_len && cols && gx && gy && x && A_re && out, "null pointer");
     DM_REQUIRE(ctx, ldx >= C && ldo >= C && lda >= C, "ldx >= C, ldo >= C, lda >= C");
     DM_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = dl_check_counts(ctx, "dm_dnet_gradfeat_f32", B, N, n_verts)) return rc;
+    if (int rc = dm_dnet_check_counts(ctx, "dm_dnet_gradfeat_f32", B, N, n_verts)) return rc;
     // the four stages, the row lengths and -- up to GF_ELL_MAX entries per row -- the tile's ELL rows (12 bytes per entry)
     const int ell_lds = nnz <= GF_ELL_MAX;
     const size_t lds = (size_t)(4 * DL_KC * DL_LD + DL_T) * 4 + (ell_lds ? (size_t)DL_T * nnz * 12 : 0);

@@ -19,15 +19,26 @@ import torch.nn as nn
 K_MAX = 1024        # the diffusion kernels' limit on k_eig (dm_dnet_diffuse_f32, dm_dnet_diffuse_bwd_f32)
 
 
-class LinearFn(torch.autograd.Function):
-    """act(concat(srcs) W^T + bias) + resid; saved: the sources (for the weight / bias gradient), W (for a source's gradient), the
-    output (relu)."""
+def _same(A):
+    return A
 
-    @staticmethod
-    def forward(ctx, eng, nv, relu, W, bias, resid, *srcs):
+
+def _rounded(A):
+    """a float32 master matrix rounded to float16 for this call (None stays None)"""
+    return None if A is None else A.detach().to(torch.float16)
+
+
+class LinearFn(torch.autograd.Function):
+    """act(concat(srcs) W^T + bias) + resid; saved: the sources (for the weight / bias gradient), W as the kernels read it (for a
+    source's gradient), the output (relu)."""
+    fwd, bwd, matrix = "dnet_linear", "dnet_linear_backward", staticmethod(_same)      # the engine's methods; W as the kernels read it
+
+    @classmethod
+    def forward(cls, ctx, eng, nv, relu, W, bias, resid, *srcs):
         if relu and resid is not None:
-            raise ValueError("LinearFn: relu with resid is not differentiated (the saved output would not show the mask)")
-        y = eng.dnet_linear(list(srcs), W, bias, resid, relu=relu, n_verts=nv)
+            raise ValueError(f"{cls.__name__}: relu with resid is not differentiated (the saved output would not show the mask)")
+        W = cls.matrix(W)
+        y = getattr(eng, cls.fwd)(list(srcs), W, bias, resid, relu=relu, n_verts=nv)
         need = ctx.needs_input_grad
         ctx.eng, ctx.nv, ctx.relu = eng, nv, relu
         ctx.widths = [int(s.shape[-1]) for s in srcs]
@@ -35,118 +46,77 @@ class LinearFn(torch.autograd.Function):
         ctx.save_for_backward(*((list(srcs) if ctx.keep_srcs else []) + ([W] if ctx.keep_W else []) + ([y] if relu else [])))
         return y
 
-    @staticmethod
-    def backward(ctx, dy):
+    @classmethod
+    def backward(cls, ctx, dy):
         need, saved = ctx.needs_input_grad, list(ctx.saved_tensors)
         y = saved.pop() if ctx.relu else None
         W = saved.pop() if ctx.keep_W else None
         srcs = saved if ctx.keep_srcs else ctx.widths
-        d_src, dW, db = ctx.eng.dnet_linear_backward(dy, srcs, W, y=y, n_verts=ctx.nv, need_src=list(need[6:]), need_weight=need[3], need_bias=need[4])
+        d_src, dW, db = getattr(ctx.eng, cls.bwd)(dy, srcs, W, y=y, n_verts=ctx.nv, need_src=list(need[6:]), need_weight=need[3], need_bias=need[4])
         return (None, None, None, dW, db, dy if need[5] else None, *d_src)
 
 
 class DiffuseFn(torch.autograd.Function):
     """the spectral diffusion of x with the (clamped) times; saved: the times, and x for the gradient of the times"""
+    fwd, bwd = "dnet_diffuse", "dnet_diffuse_backward"
 
     @staticmethod
-    def forward(ctx, eng, packed, x, times):
-        out = eng.dnet_diffuse(x, packed.mass, packed.evals, packed.evecs, times, n_verts=packed.n_verts_dev)
+    def operands(packed):                      # what the engine's two methods take between x and the times
+        return packed.mass, packed.evals, packed.evecs
+
+    @classmethod
+    def forward(cls, ctx, eng, packed, x, times):
+        out = getattr(eng, cls.fwd)(x, *cls.operands(packed), times, n_verts=packed.n_verts_dev)
         ctx.eng, ctx.packed = eng, packed
         ctx.save_for_backward(times, *([x] if ctx.needs_input_grad[3] else []))
         return out
 
-    @staticmethod
-    def backward(ctx, d_out):
+    @classmethod
+    def backward(cls, ctx, d_out):
         need, p = ctx.needs_input_grad, ctx.packed
         times, x = (list(ctx.saved_tensors) + [None])[:2]
-        dx, dt = ctx.eng.dnet_diffuse_backward(d_out, x, p.mass, p.evals, p.evecs, times, n_verts=p.n_verts_dev, need_x=need[2], need_times=need[3])
+        dx, dt = getattr(ctx.eng, cls.bwd)(d_out, x, *cls.operands(p), times, n_verts=p.n_verts_dev, need_x=need[2], need_times=need[3])
         return None, None, dx, dt
 
 
 class GradFeatFn(torch.autograd.Function):
-    """SpatialGradientFeatures of the diffused features x; saved: x and the matrices"""
+    """SpatialGradientFeatures of the diffused features x; saved: x and the matrices as the kernels read them"""
+    fwd, bwd, matrix = "dnet_gradient_features", "dnet_gradient_features_backward", staticmethod(_same)
 
-    @staticmethod
-    def forward(ctx, eng, packed, x, A_re, A_im):
-        out = eng.dnet_gradient_features(x, packed.row_len, packed.cols, packed.gx, packed.gy, A_re, A_im, n_verts=packed.n_verts_dev)
+    @classmethod
+    def forward(cls, ctx, eng, packed, x, A_re, A_im):
+        A_re, A_im = cls.matrix(A_re), cls.matrix(A_im)
+        out = getattr(eng, cls.fwd)(x, packed.row_len, packed.cols, packed.gx, packed.gy, A_re, A_im, n_verts=packed.n_verts_dev)
         ctx.eng, ctx.packed, ctx.rot = eng, packed, A_im is not None
         ctx.save_for_backward(x, A_re, *([A_im] if ctx.rot else []))
         return out
 
-    @staticmethod
-    def backward(ctx, d_out):
+    @classmethod
+    def backward(cls, ctx, d_out):
         need, p = ctx.needs_input_grad, ctx.packed
         x, A_re, A_im = (list(ctx.saved_tensors) + [None])[:3]
-        dx, dA_re, dA_im = ctx.eng.dnet_gradient_features_backward(d_out, x, p.row_len, p.cols, p.gx, p.gy, p.transposed_rows() if need[2] else None,
-                                                                   A_re, A_im, n_verts=p.n_verts_dev, need_x=need[2], need_A=bool(need[3] or need[4]))
+        dx, dA_re, dA_im = getattr(ctx.eng, cls.bwd)(d_out, x, p.row_len, p.cols, p.gx, p.gy, p.transposed_rows() if need[2] else None, A_re, A_im,
+                                                     n_verts=p.n_verts_dev, need_x=need[2], need_A=bool(need[3] or need[4]))
         return None, None, dx, dA_re if need[3] else None, dA_im if need[4] else None
 
 
-class LinearHalfFn(torch.autograd.Function):
+class LinearHalfFn(LinearFn):
     """LinearFn with the float32 master W rounded to float16 for this call; saved: the sources, the float16 copy, the output (relu)"""
-
-    @staticmethod
-    def forward(ctx, eng, nv, relu, W, bias, resid, *srcs):
-        if relu and resid is not None:
-            raise ValueError("LinearHalfFn: relu with resid is not differentiated (the saved output would not show the mask)")
-        W_h = W.detach().to(torch.float16)
-        y = eng.dnet_linear_f16(list(srcs), W_h, bias, resid, relu=relu, n_verts=nv)
-        need = ctx.needs_input_grad
-        ctx.eng, ctx.nv, ctx.relu = eng, nv, relu
-        ctx.widths = [int(s.shape[-1]) for s in srcs]
-        ctx.keep_srcs, ctx.keep_W = bool(need[3] or (bias is not None and need[4])), any(need[6:])
-        ctx.save_for_backward(*((list(srcs) if ctx.keep_srcs else []) + ([W_h] if ctx.keep_W else []) + ([y] if relu else [])))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        need, saved = ctx.needs_input_grad, list(ctx.saved_tensors)
-        y = saved.pop() if ctx.relu else None
-        W_h = saved.pop() if ctx.keep_W else None
-        srcs = saved if ctx.keep_srcs else ctx.widths
-        d_src, dW, db = ctx.eng.dnet_linear_backward_f16(dy, srcs, W_h, y=y, n_verts=ctx.nv, need_src=list(need[6:]), need_weight=need[3],
-                                                         need_bias=need[4])
-        return (None, None, None, dW, db, dy if need[5] else None, *d_src)
+    fwd, bwd, matrix = "dnet_linear_f16", "dnet_linear_backward_f16", staticmethod(_rounded)
 
 
-class DiffuseHalfFn(torch.autograd.Function):
+class DiffuseHalfFn(DiffuseFn):
     """DiffuseFn on the pack's half_operands(); saved: the times, and x for the gradient of the times"""
+    fwd, bwd = "dnet_diffuse_f16", "dnet_diffuse_backward_f16"
 
     @staticmethod
-    def forward(ctx, eng, packed, x, times):
-        out = eng.dnet_diffuse_f16(x, *packed.half_operands(), packed.evals, times, n_verts=packed.n_verts_dev)
-        ctx.eng, ctx.packed = eng, packed
-        ctx.save_for_backward(times, *([x] if ctx.needs_input_grad[3] else []))
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        need, p = ctx.needs_input_grad, ctx.packed
-        times, x = (list(ctx.saved_tensors) + [None])[:2]
-        dx, dt = ctx.eng.dnet_diffuse_backward_f16(d_out, x, *p.half_operands(), p.evals, times, n_verts=p.n_verts_dev, need_x=need[2],
-                                                   need_times=need[3])
-        return None, None, dx, dt
+    def operands(packed):
+        return (*packed.half_operands(), packed.evals)
 
 
-class GradFeatHalfFn(torch.autograd.Function):
+class GradFeatHalfFn(GradFeatFn):
     """GradFeatFn with the float32 masters A_re / A_im rounded to float16 for this call; saved: x and the float16 copies"""
-
-    @staticmethod
-    def forward(ctx, eng, packed, x, A_re, A_im):
-        A_re_h, A_im_h = A_re.detach().to(torch.float16), None if A_im is None else A_im.detach().to(torch.float16)
-        out = eng.dnet_gradient_features_f16(x, packed.row_len, packed.cols, packed.gx, packed.gy, A_re_h, A_im_h, n_verts=packed.n_verts_dev)
-        ctx.eng, ctx.packed, ctx.rot = eng, packed, A_im is not None
-        ctx.save_for_backward(x, A_re_h, *([A_im_h] if ctx.rot else []))
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        need, p = ctx.needs_input_grad, ctx.packed
-        x, A_re_h, A_im_h = (list(ctx.saved_tensors) + [None])[:3]
-        dx, dA_re, dA_im = ctx.eng.dnet_gradient_features_backward_f16(d_out, x, p.row_len, p.cols, p.gx, p.gy, p.transposed_rows() if need[2] else None,
-                                                                       A_re_h, A_im_h, n_verts=p.n_verts_dev, need_x=need[2],
-                                                                       need_A=bool(need[3] or need[4]))
-        return None, None, dx, dA_re if need[3] else None, dA_im if need[4] else None
+    fwd, bwd, matrix = "dnet_gradient_features_f16", "dnet_gradient_features_backward_f16", staticmethod(_rounded)
 
 
 def run(net, eng, xs, packed, half=False):
